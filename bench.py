@@ -9,12 +9,22 @@ the RFC test keys of org/zeromq/ZMQ.java:4603-4624), counters 3.., every 8th
 frame MORE.  Payload bytes: counter-based SplitMix64, generated on device.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4k|100b|zipf|zipf_lane|open4k|e2e4k]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does only what `value` needs: it builds the batch, ramps and warms up, times the K
+steps, writes its outputs if --dump-outputs is given, and prints the line.  --full adds everything
+else the line can carry, each in runs of its own outside the timed steps: the oracle parity spot
+check, the device copy ceiling (roofline.hbm_copy_GBps), the freshness of the committed counters
+(roofline.pmc_build), `seal_open_verify`, `cpu_baseline`, and at N > 1 the scatter -> seal ->
+gather leg.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(float32 / float64; a fixed, seeded sample of the frames, the same for every run with the same
+arguments), so that two builds can be compared output for output.
 
 N > 1 (torch.distributed.run, one rank per GPU): every rank seals its own 2^20
 frames (counters offset by rank * 2^20): no collective on the timed path ("weak"); barriers and
 the max-over-ranks timing run on a gloo control group.  Rank 0 prints ONE JSON line.  `value` =
-payload GiB/s over all ranks.  The 4k line also carries `seal_open_verify` (configs[4]: seal, then
-open + tag-verify of the same frames, timed apart from `value`).  At N > 1 the RCCL scatter ->
+payload GiB/s over all ranks.  With --full the 4k line also carries `seal_open_verify` (configs[4]: seal, then
+open + tag-verify of the same frames, timed apart from `value`), and at N > 1 the RCCL scatter ->
 seal -> gather leg runs AFTER that line is out, under a watchdog; rank 0 prints its result on a
 `SCATTER_GATHER {...}` line (not a JSON line), which `python bench.py --gpus N` merges into the
 line it relays.
@@ -62,15 +72,22 @@ def parse():
                                                           "engine", "nacl", "beforenm", "jni"])
     ap.add_argument("--frames", type=int, default=FRAMES)
     ap.add_argument("--chunk-frames", type=int, default=16384, help="e2e4k: frames per pipeline chunk")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the oracle parity spot check, the "
+                         "copy ceiling, the counters' freshness, seal_open_verify, the CPU baseline and, at "
+                         "N > 1, the scatter/gather leg (each can be left out again with its --no-... option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy "
+                         "(float32 / float64, a fixed seeded sample of the frames, under 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-scatter", action="store_true",
-                    help="N>1, 4k: skip the separately timed RCCL scatter -> seal -> gather leg")
+                    help="--full, N>1, 4k: skip the separately timed RCCL scatter -> seal -> gather leg")
     ap.add_argument("--leg-deadline", type=float, default=LEG_DEADLINE_S,
                     help="N>1: seconds the scatter/gather leg may take after the main line before the ranks exit")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the parity spot check (diagnostic builds with CZ_DIAG_* only)")
+                    help="--full: skip the parity spot check (diagnostic builds with CZ_DIAG_* only)")
     ap.add_argument("--no-roundtrip", action="store_true",
-                    help="4k: skip the separately timed seal -> open+verify leg (BASELINE.json configs[4])")
+                    help="--full, 4k: skip the separately timed seal -> open+verify leg (BASELINE.json configs[4])")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-baseline sample duration")
     return ap.parse_args()
 
@@ -121,7 +138,7 @@ def launch_ranks(gpus, argv, popen=None, cmd=None, kill=None, leg_deadline_s=LAU
     and never execs: the ranks are its children.
 
     The main line is checked before it is relayed: exactly one JSON line, n_gpus == N, one per_rank
-    entry per rank, the slowest-rank roofline and the CPU baseline; anything else is an error (the
+    entry per rank, the slowest-rank roofline and, of a --full run, the CPU baseline; anything else is an error (the
     child's exit status, or 1), so a run that silently timed fewer GPUs cannot pass.  After the main
     line the ranks run the RCCL scatter/gather leg: its SG_TAG line is merged into the relayed line
     as "scatter_gather".  If the leg has not reported within leg_deadline_s of the main line, the
@@ -189,7 +206,9 @@ def launch_ranks(gpus, argv, popen=None, cmd=None, kill=None, leg_deadline_s=LAU
     # kernel time (with the per-rank spread) and the CPU baseline
     roof = line.get("roofline") or {}
     missing = [k for k in ("achieved", "frac", "frac_min", "frac_max", "kernel_ms_max") if roof.get(k) is None]
-    if "--no-cpu-baseline" not in argv and not line.get("cpu_baseline"):
+    # the CPU baseline belongs to a --full line (a line that does not say which it is counts as one)
+    full = "--full" in argv or line.get("full", True)
+    if full and "--no-cpu-baseline" not in argv and not line.get("cpu_baseline"):
         missing.append("cpu_baseline")
     if line.get("value") is not None and missing:
         print(f"rank line lacks {missing}", file=sys.stderr)
@@ -1071,6 +1090,56 @@ def roundtrip_leg(wl, world, steps):
             "payload_GiBps": round(total / elapsed / 2**30, 3), "verified": bool(ok)}
 
 
+DUMP_FRAMES = 2048          # frames in a dump's sample: 2048 x 4129 B as float32 = 34 MB
+DUMP_MAX_BYTES = 12 << 20   # Zipf: sampled bodies stop here (48 MB as float32)
+
+
+def dump_outputs(wl, out_dir, rank=0, world=1):
+    """--dump-outputs: what the last timed step left in the caller's output buffers, as
+    out_dir/<name>.npy (rank r of N > 1: <name>_rank<r>.npy).  The sample is fixed: the first and the
+    last frame and DUMP_FRAMES frame indices drawn with seed 0x0D5EED, in rising order, the same for every
+    run with the same arguments; only the bytes a caller reads are taken (the body or the payload of
+    each sampled frame, never slot padding).  Byte values as float32, indices as float64.  Seal
+    configs: `bodies` (4k / 100b: [sample, 33 + n]; Zipf: the sampled bodies end to end, with
+    `body_offsets`).  Open configs: `payloads` the same way and `status` of every frame (rc in the low
+    byte, the flags byte in the high one)."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    k = min(wl.count, DUMP_FRAMES)
+    idx = np.concatenate(([0, wl.count - 1], np.random.default_rng(0x0D5EED).choice(wl.count, size=k, replace=False)))
+    arrays = {}
+    opens = wl.cfg in ("open4k", "zipf_open")
+    if wl.n is None:       # Zipf: as many of the drawn frames, in the order drawn, as fit the byte limit
+        drawn = wl.desc_np["len"][idx].astype(np.int64) + (0 if opens else 33)
+        idx = idx[np.cumsum(drawn) <= DUMP_MAX_BYTES]
+    idx = np.unique(idx).astype(np.int64)
+    if wl.n is not None:   # uniform slots
+        if opens:
+            buf, stride, width = wl.d_plain, wl.plain_stride, wl.n
+        else:
+            buf, stride, width = wl.d_out, wl.out_stride, wl.n + 33
+        rows = buf.view(wl.count, stride).index_select(0, torch.from_numpy(idx).to(wl.dev))[:, :width]
+        arrays["payloads" if opens else "bodies"] = rows.cpu().numpy().astype(np.float32)
+    else:                  # Zipf: every frame at its own offset, its own length
+        off = wl.desc_np["in_off" if opens else "out_off"].astype(np.int64)
+        length = wl.desc_np["len"].astype(np.int64) + (0 if opens else 33)
+        buf = wl.d_plain if opens else wl.d_out
+        parts = [buf[int(off[i]):int(off[i] + length[i])] for i in idx]
+        arrays["payloads" if opens else "bodies"] = torch.cat(parts).cpu().numpy().astype(np.float32)
+        ends = np.cumsum(length[idx])
+        arrays["payload_offsets" if opens else "body_offsets"] = (ends - length[idx]).astype(np.float64)
+    if opens:
+        arrays["status"] = wl.status.cpu().numpy().view(np.uint16).astype(np.float32)
+    arrays["frame_index"] = idx.astype(np.float64)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    total = 0
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64 << 20, total
+    return {"dir": out_dir, "arrays": sorted(arrays), "frames": int(len(idx)), "bytes": total}
+
+
 def jni_host(args):
     """The host path timed THROUGH the JNI shim (north star: the end-to-end rate including the JNI
     pinned-buffer copies): tools/bin/jni_bench (jni/jni_bench.c, built by __graft_entry__.build)
@@ -1102,6 +1171,8 @@ def jni_host(args):
 
 def main():
     args = parse()
+    if args.dump_outputs and args.config in ("e2e4k", "engine", "beforenm", "nacl", "jni"):
+        sys.exit(f"--dump-outputs covers the device-resident configs, not --config {args.config}")
     if args.config == "jni":
         sys.exit(jni_host(args))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1128,7 +1199,7 @@ def main():
     for _ in range(args.warmup):
         wl.step()
     torch.cuda.synchronize()
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         wl.verify_sample()
 
     stream = torch.cuda.current_stream()
@@ -1167,22 +1238,23 @@ def main():
     roof_k = multi_rank_roofline(kernel_s, alg_bytes)  # N = 1: this rank's own kernel time
     achieved = roof_k["achieved"]
     slow_kernel_s = max(kernel_s)
-    copy_gbs, torch_copy_gbs = hbm_copy_ceiling(dev) if rank == 0 else (None, None)
+    dumped = dump_outputs(wl, args.dump_outputs, rank, world) if args.dump_outputs else None
+    copy_gbs, torch_copy_gbs = hbm_copy_ceiling(dev) if rank == 0 and args.full else (None, None)
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from pmc_key import key_from_args
     pmc_key = key_from_args(args)
     pmc = load_pmc(pmc_key)
     traffic = pmc.get("hbm_bytes_per_launch")
-    pmc_build = pmc_freshness(pmc)
+    pmc_build = pmc_freshness(pmc) if args.full else None
 
-    want_leg = world > 1 and args.config == "4k" and not args.no_scatter
+    want_leg = args.full and world > 1 and args.config == "4k" and not args.no_scatter
 
     rtl = None
-    if args.config == "4k" and not args.no_roundtrip:
+    if args.full and args.config == "4k" and not args.no_roundtrip:
         rtl = roundtrip_leg(wl, world, min(args.steps, 10))
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # at N > 1 too, on rank 0 after every timed leg (the other ranks wait at the barrier below)
         cpu = cpu_baseline(wl, args.cpu_seconds)
         if world > 1:
@@ -1210,6 +1282,7 @@ def main():
             "ramp_steps": ramp,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True,
+            "full": bool(args.full),
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": "u32",
@@ -1244,6 +1317,8 @@ def main():
         }
         if rtl is not None:
             line["seal_open_verify"] = rtl
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if want_leg:  # run after this line is out; rank 0 prints its result on an SG_TAG line
             line["scatter_gather"] = {"pending": True, "reported_on": SG_TAG.strip() + " line",
                                       "deadline_s": args.leg_deadline}

@@ -101,7 +101,7 @@ def test_bench_ws2_rehearsal():
     env = dict(os.environ, CZ_DIST_BACKEND="gloo", TMPDIR="/tmp")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2",
-           "--steps", "3", "--warmup", "1", "--ramp-ms", "0", "--frames", "65536", "--cpu-seconds", "1"]
+           "--full", "--steps", "3", "--warmup", "1", "--ramp-ms", "0", "--frames", "65536", "--cpu-seconds", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -134,7 +134,7 @@ def test_bench_plain_gpus2_launches_its_own_ranks():
     env = dict(os.environ, CZ_DIST_BACKEND="gloo", TMPDIR="/tmp")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1",
            "--ramp-ms", "0", "--frames", "65536", "--cpu-seconds", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

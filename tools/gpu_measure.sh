@@ -24,29 +24,27 @@ run() {  # name, bench args
   timeout -k 10 300 python bench.py "$@" > gpurun_out/bench_$name.log 2>&1 || { tail gpurun_out/bench_$name.log; exit 4; }
   tail -1 gpurun_out/bench_$name.log | cut -c1-400
 }
-run 4k --config 4k
-run 4k_dense --config 4k_dense --no-cpu-baseline
-run 4k_box --config 4k_box --no-cpu-baseline
-run 100b --config 100b --no-cpu-baseline
-run zipf --config zipf --no-cpu-baseline
-run zipf_oa8 --config zipf --in-align 8 --out-align 8 --no-cpu-baseline
-run zipf_oa1 --config zipf --out-align 1 --no-cpu-baseline
-run open4k --config open4k --no-cpu-baseline
-run zipf_lane --config zipf_lane --no-cpu-baseline
-run zipf_open --config zipf_open --no-cpu-baseline
-run zipf_open_oa8 --config zipf_open --in-align 8 --out-align 8 --no-cpu-baseline
-run open4k_dense --config open4k --out-stride 4129 --no-cpu-baseline
-run open4k_dense8 --config open4k --out-stride 4136 --no-cpu-baseline
-run open4k_ps4224 --config open4k --plain-stride 4224 --no-cpu-baseline
-run 100b_packed --config 100b --in-stride 100 --no-cpu-baseline
-run 4k_in4097 --config 4k --in-stride 4097 --no-cpu-baseline
+run 4k --full --config 4k
+run 4k_dense --full --config 4k_dense --no-cpu-baseline
+run 4k_box --full --config 4k_box --no-cpu-baseline
+run 100b --full --config 100b --no-cpu-baseline
+run zipf --full --config zipf --no-cpu-baseline
+run zipf_oa8 --full --config zipf --in-align 8 --out-align 8 --no-cpu-baseline
+run zipf_oa1 --full --config zipf --out-align 1 --no-cpu-baseline
+run open4k --full --config open4k --no-cpu-baseline
+run zipf_lane --full --config zipf_lane --no-cpu-baseline
+run zipf_open --full --config zipf_open --no-cpu-baseline
+run zipf_open_oa8 --full --config zipf_open --in-align 8 --out-align 8 --no-cpu-baseline
+run open4k_dense --full --config open4k --out-stride 4129 --no-cpu-baseline
+run open4k_dense8 --full --config open4k --out-stride 4136 --no-cpu-baseline
+run open4k_ps4224 --full --config open4k --plain-stride 4224 --no-cpu-baseline
+run 100b_packed --full --config 100b --in-stride 100 --no-cpu-baseline
+run 4k_in4097 --full --config 4k --in-stride 4097 --no-cpu-baseline
 for cfg in e2e4k engine beforenm nacl jni; do
-  run $cfg --steps 10 --warmup 2 --config $cfg --no-cpu-baseline
+  run $cfg --full --steps 10 --warmup 2 --config $cfg --no-cpu-baseline
 done
 # the N > 1 launcher, control plane and leg at 4 ranks on this one GPU (gloo; RCCL needs 4 GPUs)
-echo "== bench --gpus 4 (gloo rehearsal)"
-CZ_DIST_BACKEND=gloo timeout -k 10 600 python bench.py --gpus 4 --frames 262144 --steps 5 --warmup 2 --ramp-ms 0 --cpu-seconds 1 > gpurun_out/bench_gpus4_gloo.log 2>&1 || { tail gpurun_out/bench_gpus4_gloo.log; exit 4; }
-tail -1 gpurun_out/bench_gpus4_gloo.log | cut -c1-400
+CZ_DIST_BACKEND=gloo run gpus4_gloo --full --gpus 4 --frames 262144 --steps 5 --warmup 2 --ramp-ms 0 --cpu-seconds 1
 fi
 if has trace; then
 for key in 4k zipf open4k 100b 4k_dense 4k_box zipf@ia8,oa8 zipf@oa1 zipf_open@ia8,oa8 open4k@os4129 open4k@os4136; do
