@@ -389,7 +389,8 @@ __device__ __forceinline__ F26 f26_from32(u32 h0, u32 h1, u32 h2, u32 h3, u32 h4
     return a;
 }
 
-// a * b mod p (partially reduced: limbs < 2^26 except l[1] < 2^26 + 2^6); inputs' limbs < 2^27
+// a * b mod p (partially reduced: limbs < 2^26 except l[1] < 2^26 + 2^7: the top column is below
+// 5 * 2^54 plus a small carry, so 5 * (d4 >> 26) adds at most 101 to l[1]); inputs' limbs < 2^27
 __device__ __forceinline__ F26 f26_mul(const F26 &a, const F26 &b)
 {
     const u32 s1 = b.l[1] * 5u, s2 = b.l[2] * 5u, s3 = b.l[3] * 5u, s4 = b.l[4] * 5u;
@@ -444,7 +445,10 @@ __device__ __forceinline__ F26 f26_pow(const F26 &r, u32 e)
     return acc;
 }
 
-// back to 32-bit limbs h0..h3 + small h4 (input for poly_finish)
+// back to 32-bit limbs h0..h3 + small h4 (input for poly_finish).  Input: an f26_add result (limbs
+// below 2^26, l[1] <= 2^26).  Then a carry out of l[4] means l[1] was 2^26 and is now 0, so the
+// last `l1 += c` stays below 2^26 and the packing below loses nothing; f26_from32 of a record with
+// h4 = 4 (l[4] >= 2^26) can end with l1 = 2^26 and must not come here (tests/test_f26_radix26.py).
 __device__ __forceinline__ void f26_to32(const F26 &a, u32 &h0, u32 &h1, u32 &h2, u32 &h3, u32 &h4)
 {
     u32 l0 = a.l[0], l1 = a.l[1], l2 = a.l[2], l3 = a.l[3], l4 = a.l[4], c;

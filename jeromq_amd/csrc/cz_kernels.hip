@@ -2498,8 +2498,14 @@ __device__ __forceinline__ void combine_tag(const u32 *__restrict__ R0, u32 nseg
         }
         H = f26_add(f26_mul(H, pl), hl);
     }
+    // A frame in one segment (a caller-built plan) finishes its record as it stands: f26_to32
+    // takes f26_add results only, and a record with h4 = 4 is none (cz_device.h).
     Poly Q;
-    f26_to32(H, Q.h0, Q.h1, Q.h2, Q.h3, Q.h4);
+    if (nseg > 1u) {
+        f26_to32(H, Q.h0, Q.h1, Q.h2, Q.h3, Q.h4);
+    } else {
+        Q.h0 = R0[0]; Q.h1 = R0[1]; Q.h2 = R0[2]; Q.h3 = R0[3]; Q.h4 = R0[4];
+    }
     Q.p0 = R0[12]; Q.p1 = R0[13]; Q.p2 = R0[14]; Q.p3 = R0[15];
     poly_finish(Q, tag);
 }

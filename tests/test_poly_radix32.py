@@ -7,7 +7,9 @@ against the big-integer definition (h + m) * r mod 2^130 - 5, over adversarial i
 Two reductions are restated: the shipped one-chain form (the 2^130 == 5 fold and the column
 carries in one v_addc_co_u32 chain) and the round-1/2 two-chain form it replaced (column
 carries, then the fold in a second chain).  The GPU parity tests pin the compiled kernels
-against the oracle.
+against the oracle on random data; tests/test_gpu_poly_edges.py runs them on inputs steered into
+the rare carries and reductions (tests/poly_steer.py, which tracks the device's limbs with
+poly_block below).
 """
 import random
 
