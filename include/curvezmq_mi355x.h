@@ -448,6 +448,62 @@ int cz_engine_add_session(cz_engine *e, const cz_hs *hs);
 int cz_zmtp_metadata_check(const uint8_t *buf, uint64_t len, int socket_type);
 uint32_t cz_zmtp_metadata(int socket_type, const uint8_t *identity, uint32_t identity_len, uint8_t *out, uint32_t cap);
 
+/* ---- 11. batched server handshake: N HELLO -> N WELCOME, N INITIATE -> N READY ---------------------
+ * The server half of the CURVE handshake (CurveServerMechanism.java:254-517: processHello :254-299,
+ * produceWelcome :301-358, processInitiate :360-471, produceReady :473-507, produceError :509-517) for
+ * many connections per call: a reconnect storm in front of a ROUTER / XPUB is accepted in two device
+ * stages whose launch count does not depend on the number of connections, and ends in sessions
+ * cz_engine takes.  Each item behaves as one cz_hs server object (section 10, no ZAP handler) fed the
+ * same command, with two differences: a slot that has seen an INITIATE, accepted or not, takes no
+ * second one (CZ_EINVAL), and a failed slot stays allocated until cz_acceptor_release.
+ * Not thread-safe: one acceptor per IO thread, as cz_engine.  No device: cz_acceptor_create returns
+ * CZ_EHIP.  ZAP is out of scope: apply an allow-list with cz_acceptor_client_key before sending READY. */
+typedef struct cz_acceptor cz_acceptor;
+typedef struct cz_accept_result { /* one per command of a batch */
+    int32_t rc;         /* CZ_OK, CZ_EPROTO, CZ_EINVAL (bad slot / incompatible Socket-Type), CZ_EAGAIN (table full) */
+    int32_t event;      /* the ZMQ_PROTOCOL_ERROR_* event cz_hs would report, else 0 */
+    int32_t slot;       /* pending-connection handle (>= 0) or -1 */
+    uint32_t reply_len; /* bytes written to this command's reply slot (0 = nothing to send) */
+} cz_accept_result;
+/* CurveServerMechanism's constructor :55-75 for max_pending connections in flight; socket_type and
+ * identity as cz_hs_create (the READY metadata) */
+int cz_acceptor_create(cz_acceptor **a, const uint8_t secret_key[32], int socket_type, const uint8_t *identity,
+                       uint32_t identity_len, uint32_t max_pending, int device);
+void cz_acceptor_destroy(cz_acceptor *a);
+/* Stage 1, processHello + produceWelcome / produceError (:254-358, :509-517).  cmds: count command
+ * bodies at off[i], size[i], all inside [0, cmds_bytes); reply: count slots of reply_stride (>= 168)
+ * bytes.  Per item: a wrong name -> CZ_EPROTO / CZ_ZMTP_UNEXPECTED_COMMAND, a size other than 200 or a
+ * version other than 1.0 -> CZ_EPROTO / CZ_ZMTP_MALFORMED_COMMAND_HELLO (no reply, no slot); a box that
+ * does not open -> CZ_OK with event CZ_ZMTP_CRYPTOGRAPHIC, the 7-byte ERROR command as reply, no slot;
+ * a good HELLO -> the 168-byte WELCOME and a slot; CZ_EAGAIN when max_pending slots are in use.
+ * test_secrets (count x 32) / test_entropy (count x 64: cookie nonce 16, cookie key 32, WELCOME nonce
+ * 16 -- cz_hs_create's order): NULL in production (getrandom).  Bad arguments (null pointers, a command
+ * outside cmds_bytes, a short stride): CZ_EINVAL for the call, nothing written. */
+int cz_acceptor_hello(cz_acceptor *a, uint32_t count, const uint8_t *cmds, uint64_t cmds_bytes, const uint64_t *off,
+                      const uint32_t *size, uint8_t *reply, uint64_t reply_stride, cz_accept_result *res,
+                      const uint8_t *test_secrets, const uint8_t *test_entropy);
+/* Stage 2, processInitiate + produceReady (:360-507) for pending slots (slot[i] from stage 1);
+ * reply_stride >= 288.  Per item: events as cz_hs (CZ_ZMTP_MALFORMED_COMMAND_INITIATE for a size below
+ * 257 or a box over 16 + 144 + 256, CZ_ZMTP_CRYPTOGRAPHIC for a cookie, INITIATE box or vouch that does
+ * not open or a cookie of another connection, CZ_ZMTP_KEY_EXCHANGE for a vouch naming another C'),
+ * CZ_EPROTO / CZ_EINVAL from the metadata (Metadata.read, the Socket-Type check), else the READY
+ * command (nonce 1).  CZ_EINVAL for a slot that is not waiting for its INITIATE. */
+int cz_acceptor_initiate(cz_acceptor *a, uint32_t count, const int32_t *slot, const uint8_t *cmds, uint64_t cmds_bytes,
+                         const uint64_t *off, const uint32_t *size, uint8_t *reply, uint64_t reply_stride,
+                         cz_accept_result *res);
+/* after a CZ_OK stage 2: the same facts cz_hs_session / cz_hs_client_key / cz_hs_peer_property give */
+int cz_acceptor_session(const cz_acceptor *a, int32_t slot, uint8_t precom[32], uint64_t *cn_nonce,
+                        uint64_t *cn_peer_nonce);
+int cz_acceptor_client_key(const cz_acceptor *a, int32_t slot, uint8_t key[32]);
+int cz_acceptor_peer_property(const cz_acceptor *a, int32_t slot, const char *name, const uint8_t **value,
+                              uint32_t *len);
+/* as cz_engine_add_session: returns the connection id */
+int cz_engine_add_accepted(cz_engine *e, const cz_acceptor *a, int32_t slot);
+/* wipe the slot's secrets (host and device) and free it for reuse */
+int cz_acceptor_release(cz_acceptor *a, int32_t slot);
+/* slots in use (handed out by stage 1 and not yet released) */
+uint32_t cz_acceptor_pending(const cz_acceptor *a);
+
 /* ---- 6. misc -------------------------------------------------------------- */
 const char *cz_last_error(void);
 const char *cz_version(void);

@@ -80,6 +80,11 @@ class cz_v2_item(ctypes.Structure):
 
 assert ctypes.sizeof(cz_v2_frame) == 16 and ctypes.sizeof(cz_v2_item) == 24
 
+
+class cz_accept_result(ctypes.Structure):
+    _fields_ = [("rc", ctypes.c_int32), ("event", ctypes.c_int32), ("slot", ctypes.c_int32),
+                ("reply_len", ctypes.c_uint32)]
+
 _VP = ctypes.c_void_p
 _P = ctypes.c_char_p
 _U8P = ctypes.POINTER(ctypes.c_uint8)
@@ -168,6 +173,17 @@ SIGNATURES = {
     "cz_hs_peer_property": (_I, [_VP, ctypes.c_char_p, ctypes.POINTER(_VP), ctypes.POINTER(_U32)]),
     "cz_hs_mechanism": (_VP, [_VP, _I]),
     "cz_engine_add_session": (_I, [_VP, _VP]),
+    "cz_acceptor_create": (_I, [ctypes.POINTER(_VP), _VP, _I, _VP, _U32, _U32, _I]),
+    "cz_acceptor_destroy": (None, [_VP]),
+    "cz_acceptor_hello": (_I, [_VP, _U32, _VP, _U64, _VP, _VP, _VP, _U64, _VP, _VP, _VP]),
+    "cz_acceptor_initiate": (_I, [_VP, _U32, _VP, _VP, _U64, _VP, _VP, _VP, _U64, _VP]),
+    "cz_acceptor_session": (_I, [_VP, ctypes.c_int32, _VP, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "cz_acceptor_client_key": (_I, [_VP, ctypes.c_int32, _VP]),
+    "cz_acceptor_peer_property": (_I, [_VP, ctypes.c_int32, ctypes.c_char_p, ctypes.POINTER(_VP),
+                                       ctypes.POINTER(_U32)]),
+    "cz_engine_add_accepted": (_I, [_VP, _VP, ctypes.c_int32]),
+    "cz_acceptor_release": (_I, [_VP, ctypes.c_int32]),
+    "cz_acceptor_pending": (_U32, [_VP]),
     "cz_zmtp_metadata_check": (_I, [_VP, _U64, _I]),
     "cz_zmtp_metadata": (_U32, [_I, _VP, _U32, _VP, _U32]),
     "cz_last_error": (ctypes.c_char_p, []),

@@ -43,7 +43,13 @@ enum State {
     CONNECTED
 };
 
+}  // namespace
+
+// Shared with the batched acceptor (cz_acceptor.cpp) through cz_internal.h.
+namespace czi {
+
 // zmq/socket/Sockets.java: names by ZMQ_* type (the enum ordinal) and their compatible peers
+namespace {
 struct SockType {
     const char *name;
     const char *peers[3];
@@ -59,6 +65,9 @@ const SockType SOCK_TYPES[] = {
 };
 constexpr int NSOCK = (int)(sizeof(SOCK_TYPES) / sizeof(SOCK_TYPES[0]));
 constexpr int ZMQ_REQ = 3, ZMQ_DEALER = 5, ZMQ_ROUTER = 6;
+}  // namespace
+
+int sock_types() { return NSOCK; }
 
 bool compatible(int self, const std::string &peer)
 {
@@ -109,8 +118,6 @@ void add_property(std::vector<uint8_t> &b, const char *name, const uint8_t *valu
         b.insert(b.end(), value, value + vlen);
 }
 
-typedef std::vector<std::pair<std::string, std::vector<uint8_t>>> Props;
-
 // Metadata.read + Mechanism.parseMetadata's listener: CZ_OK, CZ_EPROTO (trailing bytes that are not
 // a whole property) or CZ_EINVAL (a Socket-Type the local type is not compatible with)
 int parse_metadata(const uint8_t *buf, uint64_t len, int self_type, Props *out)
@@ -146,6 +153,18 @@ int parse_metadata(const uint8_t *buf, uint64_t len, int self_type, Props *out)
     return left > 0 ? CZ_EPROTO : CZ_OK;
 }
 
+// the metadata block a socket of this type sends in INITIATE / READY: Socket-Type and, for REQ / DEALER /
+// ROUTER, Identity
+std::vector<uint8_t> zmtp_metadata(int socket_type, const uint8_t *identity, size_t identity_len)
+{
+    std::vector<uint8_t> b;
+    const char *tn = socket_type >= 0 && socket_type < NSOCK ? SOCK_TYPES[socket_type].name : "";
+    add_property(b, "Socket-Type", (const uint8_t *)tn, (uint32_t)strlen(tn));
+    if (socket_type == ZMQ_REQ || socket_type == ZMQ_DEALER || socket_type == ZMQ_ROUTER)
+        add_property(b, "Identity", identity, (uint32_t)identity_len);
+    return b;
+}
+
 // Wipe secret bytes with stores the compiler may not drop (a memset just before delete or a
 // return is a dead store it is allowed to remove).
 void secure_wipe(void *p, size_t n)
@@ -159,7 +178,7 @@ void secure_wipe(std::vector<uint8_t> &v)
         explicit_bzero(v.data(), v.size());
 }
 
-}  // namespace
+}  // namespace czi
 
 struct cz_hs {
     bool server = false;
@@ -228,15 +247,7 @@ struct cz_hs {
         return cz_box(c.data(), m.data(), m.size(), n, pk, sk);
     }
 
-    std::vector<uint8_t> metadata() const
-    {
-        std::vector<uint8_t> b;
-        const char *tn = socket_type >= 0 && socket_type < NSOCK ? SOCK_TYPES[socket_type].name : "";
-        add_property(b, "Socket-Type", (const uint8_t *)tn, (uint32_t)strlen(tn));
-        if (socket_type == ZMQ_REQ || socket_type == ZMQ_DEALER || socket_type == ZMQ_ROUTER)
-            add_property(b, "Identity", identity.data(), (uint32_t)identity.size());
-        return b;
-    }
+    std::vector<uint8_t> metadata() const { return zmtp_metadata(socket_type, identity.data(), identity.size()); }
 
     // ---- client ----
     int produce_hello(std::vector<uint8_t> &msg)

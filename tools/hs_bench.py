@@ -1,0 +1,174 @@
+#!/usr/bin/env python3
+"""Latency of the batched CURVE server handshake (cz_acceptor) against the per-connection one (cz_hs).
+
+For N in {1, 64, 1024, 16384, 131072}: wall clock around the synchronous cz_acceptor_hello (stage 1)
+and cz_acceptor_initiate (stage 2) calls, after one warm-up round, median of --reps rounds.  The
+commands are generated once, outside the timed region, by the CPU model of tests/hs_model.py; the
+C entry points are called directly, so no Python packing is timed.  Baseline in the same run: 64
+cz_hs server objects driven one after another from construction through HELLO -> READY.
+
+Command generation: connection i uses client i % POOL and the injected server short-term secret
+i % POOL, with injected entropy, so the CPU side needs POOL key agreements, not N, and a round's
+WELCOMEs (hence the INITIATEs made from them) are the same every round.  The device work per lane
+does not depend on that.  `stage1_getrandom_ms` is stage 1 drawing its secrets and entropy from
+getrandom, as in production.
+
+Writes one JSON (default profiles/hs_batch/hs_batch.json) and prints it."""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+SERVER_PUB = bytes.fromhex("54FCBA24E93249969316FB617C872BB0C1D1FF14800427C594CBFACF1BC2D652")
+SERVER_SEC = bytes.fromhex("8E0BDD697628B91D8F245587EE95C5B04D48963F79259877B49CD9063AEAD3B7")
+POOL = 64
+SIZES = (1, 64, 1024, 16384, 131072)
+
+
+def make_pool():
+    import hs_model as M
+    from cz_testlib import splitmix_bytes
+    pool = []
+    for i in range(POOL):
+        b = splitmix_bytes(176, 990000 + i)
+        c = {"csec": b[0:32], "ceph": b[32:64], "seph": b[64:96], "entropy": b[96:160], "vnonce": b[160:176]}
+        c["cpub"] = M.public_key(c["csec"])
+        c["hello"] = M.client_hello(SERVER_PUB, c["ceph"])
+        c["welcome"], _ = M.server_welcome(c["hello"], SERVER_SEC, c["seph"], c["entropy"])
+        c["initiate"] = M.client_initiate(c["welcome"], c["cpub"], c["csec"], SERVER_PUB, c["ceph"], c["vnonce"])
+        pool.append(c)
+    return pool
+
+
+class Batch:
+    """prebuilt arguments of the two stage calls for n connections"""
+
+    def __init__(self, pool, n):
+        from jeromq_amd import _lib
+        self.n = n
+        idx = np.arange(n) % POOL
+        self.hello = np.frombuffer(b"".join(c["hello"] for c in pool), dtype=np.uint8).reshape(POOL, 200)[idx].copy()
+        ini = [c["initiate"] for c in pool]
+        self.isize = len(ini[0])
+        assert all(len(x) == self.isize for x in ini)
+        self.init = np.frombuffer(b"".join(ini), dtype=np.uint8).reshape(POOL, self.isize)[idx].copy()
+        self.secrets = np.frombuffer(b"".join(c["seph"] for c in pool), dtype=np.uint8).reshape(POOL, 32)[idx].copy()
+        self.entropy = np.frombuffer(b"".join(c["entropy"] for c in pool), dtype=np.uint8).reshape(POOL, 64)[idx].copy()
+        self.hoff = (np.arange(n, dtype=np.uint64) * np.uint64(200))
+        self.hsize = np.full(n, 200, dtype=np.uint32)
+        self.ioff = (np.arange(n, dtype=np.uint64) * np.uint64(self.isize))
+        self.isz = np.full(n, self.isize, dtype=np.uint32)
+        self.res = (_lib.cz_accept_result * n)()
+        self.reply = np.zeros(n * 288, dtype=np.uint8)
+        self.slots = np.zeros(n, dtype=np.int32)
+        self.welcome0, self.ready0 = pool[0]["welcome"], None
+
+    def stage1(self, L, acc, injected=True):
+        t0 = time.perf_counter()
+        rc = L.cz_acceptor_hello(acc, self.n, self.hello.ctypes.data, self.hello.nbytes, self.hoff.ctypes.data,
+                                 self.hsize.ctypes.data, self.reply.ctypes.data, 168, self.res,
+                                 self.secrets.ctypes.data if injected else None,
+                                 self.entropy.ctypes.data if injected else None)
+        dt = time.perf_counter() - t0
+        assert rc == 0, rc
+        r = np.frombuffer(self.res, dtype=np.int32).reshape(self.n, 4)
+        assert not r[:, 0].any() and (r[:, 3] == 168).all(), "stage 1 refused a HELLO"
+        self.slots[:] = r[:, 2]
+        if injected:
+            assert self.reply[:168].tobytes() == self.welcome0, "WELCOME 0 differs from the model's"
+        return dt
+
+    def stage2(self, L, acc):
+        t0 = time.perf_counter()
+        rc = L.cz_acceptor_initiate(acc, self.n, self.slots.ctypes.data, self.init.ctypes.data, self.init.nbytes,
+                                    self.ioff.ctypes.data, self.isz.ctypes.data, self.reply.ctypes.data, 288, self.res)
+        dt = time.perf_counter() - t0
+        assert rc == 0, rc
+        r = np.frombuffer(self.res, dtype=np.int32).reshape(self.n, 4)
+        assert not r[:, 0].any() and (r[:, 3] == r[0, 3]).all() and r[0, 3] > 30, "stage 2 refused an INITIATE"
+        return dt
+
+    def release(self, L, acc):
+        for s in self.slots.tolist():
+            L.cz_acceptor_release(acc, s)
+        assert L.cz_acceptor_pending(acc) == 0
+
+
+def serial_baseline(pool, reps):
+    """64 cz_hs servers, one after another, constructor through READY; seconds per round"""
+    from jeromq_amd import handshake
+    times = []
+    for _ in range(reps + 1):
+        t0 = time.perf_counter()
+        for c in pool:
+            srv = handshake.CurveServerHandshake(SERVER_SEC, ephemeral_secret=c["seph"], entropy=c["entropy"])
+            assert srv.processHandshakeCommand(c["hello"]) == 0
+            rc, w = srv.nextHandshakeCommand()
+            assert srv.processHandshakeCommand(c["initiate"]) == 0
+            rc, r = srv.nextHandshakeCommand()
+            assert rc == 0 and srv.status() == handshake.Status.READY
+            srv.close()
+        times.append(time.perf_counter() - t0)
+        assert w.data == pool[-1]["welcome"]
+    return times[1:]
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sizes", type=int, nargs="*", default=list(SIZES))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hs_batch", "hs_batch.json"))
+    args = ap.parse_args()
+    if args.reps < 5:
+        ap.error("--reps must be at least 5")
+    import torch
+    from jeromq_amd import _lib
+    assert torch.cuda.is_available(), "hs_bench needs a GPU"
+    L = _lib.lib()
+    pool = make_pool()
+    out = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "pool": POOL, "clock": "time.perf_counter",
+           "initiate_bytes": len(pool[0]["initiate"]), "batched": []}
+    base = serial_baseline(pool, args.reps)
+    out["serial_cz_hs"] = {"connections": POOL, "round_ms": [round(t * 1e3, 3) for t in base],
+                           "median_round_ms": round(statistics.median(base) * 1e3, 3),
+                           "median_per_connection_ms": round(statistics.median(base) * 1e3 / POOL, 4)}
+    for n in args.sizes:
+        acc = ctypes.c_void_p()
+        _lib.check(L.cz_acceptor_create(ctypes.byref(acc), SERVER_SEC, 0, None, 0, n, 0), "cz_acceptor_create")
+        b = Batch(pool, n)
+        t1, t2, t1r = [], [], []
+        for rep in range(args.reps + 1):   # round 0 warms up (buffers grow, code objects load)
+            a = b.stage1(L, acc)
+            c = b.stage2(L, acc)
+            b.release(L, acc)
+            r = b.stage1(L, acc, injected=False)
+            b.release(L, acc)
+            if rep:
+                t1.append(a)
+                t2.append(c)
+                t1r.append(r)
+        L.cz_acceptor_destroy(acc)
+        ms = lambda v: round(statistics.median(v) * 1e3, 4)  # noqa: E731
+        row = {"n": n, "stage1_ms": ms(t1), "stage2_ms": ms(t2), "stage1_getrandom_ms": ms(t1r),
+               "stage1_all_ms": [round(t * 1e3, 4) for t in t1], "stage2_all_ms": [round(t * 1e3, 4) for t in t2],
+               "per_connection_us": round((statistics.median(t1) + statistics.median(t2)) * 1e6 / n, 3)}
+        out["batched"].append(row)
+        print(f"n={n}: stage 1 {row['stage1_ms']} ms, stage 2 {row['stage2_ms']} ms", file=sys.stderr)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
