@@ -504,6 +504,69 @@ int cz_acceptor_release(cz_acceptor *a, int32_t slot);
 /* slots in use (handed out by stage 1 and not yet released) */
 uint32_t cz_acceptor_pending(const cz_acceptor *a);
 
+/* ---- 12. batched client handshake: N HELLO, N WELCOME -> N INITIATE, N READY -> N sessions ----------
+ * The client half of the CURVE handshake (CurveClientMechanism.java:246-429: produceHello :246-279,
+ * processWelcome :281-316, produceInitiate :318-385, processReady :387-419, processError :421-429) for
+ * many connections per call: a process that dials many peers (a collector in front of thousands of
+ * publishers, a broker's back end after a restart, a mesh node) connects in three device stages whose
+ * launch count does not depend on the number of connections, and ends in sessions cz_engine takes.
+ * Each item behaves as one cz_hs client object (section 10) fed the same command -- WELCOME is accepted
+ * only by a slot waiting for it and READY only by a slot waiting for that, as there -- with two
+ * differences: a slot whose WELCOME or READY was rejected, or that received an ERROR, takes no further
+ * command (CZ_EINVAL), and a failed slot stays allocated until cz_connector_release.  A slot named twice
+ * in one call: the first item takes it, the second gets CZ_EINVAL.
+ * Conventions as section 11: bad arguments (null pointers, a command outside cmds_bytes, a short
+ * stride) give CZ_EINVAL for the call with nothing written; results are cz_accept_result records.  Not
+ * thread-safe: one connector per IO thread.  No device: cz_connector_create returns CZ_EHIP. */
+typedef struct cz_connector cz_connector;
+/* CurveClientMechanism's constructor :55-78 for max_pending connections in flight.  public_key /
+ * secret_key: the client's long-term pair; socket_type and identity as cz_hs_create (the INITIATE
+ * metadata: more than 256 bytes of it is CZ_EMSGSIZE here, where cz_hs fails at INITIATE time). */
+int cz_connector_create(cz_connector **c, const uint8_t public_key[32], const uint8_t secret_key[32], int socket_type,
+                        const uint8_t *identity, uint32_t identity_len, uint32_t max_pending, int device);
+void cz_connector_destroy(cz_connector *c);
+/* Stage 1, the constructor's short-term key pair :66 and produceHello :246-279.  server_keys: count x
+ * 32 bytes, one server key per connection (a batch may dial different servers); reply: count slots of
+ * reply_stride (>= 200) bytes.  Per item: the 200-byte HELLO (nonce 1) and a slot, or CZ_EAGAIN when
+ * max_pending slots are in use.  test_secrets (count x 32 short-term secrets): NULL in production
+ * (getrandom). */
+int cz_connector_hello(cz_connector *c, uint32_t count, const uint8_t *server_keys, uint8_t *reply, uint64_t reply_stride,
+                       cz_accept_result *res, const uint8_t *test_secrets);
+/* Stage 2, processWelcome + produceInitiate (:281-385) for slots that wait for their WELCOME (slot[i]
+ * from stage 1).  cmds: count command bodies at off[i], size[i], all inside [0, cmds_bytes); reply:
+ * count slots of reply_stride (>= 513) bytes.  Per item, as cz_hs: another command's name ->
+ * CZ_EPROTO / CZ_ZMTP_UNEXPECTED_COMMAND; a size other than 168 -> CZ_ZMTP_MALFORMED_COMMAND_READY
+ * (sic); a box that does not open -> CZ_ZMTP_CRYPTOGRAPHIC; an ERROR command -> processError's result
+ * (CZ_OK with no reply for a well-formed one, its status code in cz_connector_error_status; else
+ * CZ_EPROTO / CZ_ZMTP_MALFORMED_COMMAND_ERROR or CZ_ZAP_MALFORMED_REPLY); else the INITIATE command
+ * (nonce 2, 257 + metadata bytes).  CZ_EINVAL for a slot that is not waiting for a WELCOME.
+ * test_entropy (count x 16: each item's vouch nonce): NULL in production (getrandom). */
+int cz_connector_welcome(cz_connector *c, uint32_t count, const int32_t *slot, const uint8_t *cmds, uint64_t cmds_bytes,
+                         const uint64_t *off, const uint32_t *size, uint8_t *reply, uint64_t reply_stride,
+                         cz_accept_result *res, const uint8_t *test_entropy);
+/* Stage 3, processReady (:387-419) for slots that wait for their READY.  Per item, as cz_hs: a size
+ * below 30 or a box over 16 + 16 + 256 -> CZ_ZMTP_MALFORMED_COMMAND_READY; a box that does not open ->
+ * CZ_ZMTP_CRYPTOGRAPHIC; CZ_EPROTO / CZ_EINVAL from the metadata (Metadata.read, the Socket-Type
+ * check); an ERROR command as in stage 2; else CZ_OK and the slot holds a session.  reply_len is 0. */
+int cz_connector_ready(cz_connector *c, uint32_t count, const int32_t *slot, const uint8_t *cmds, uint64_t cmds_bytes,
+                       const uint64_t *off, const uint32_t *size, cz_accept_result *res);
+/* after a CZ_OK stage 3: the same facts cz_hs_session / cz_hs_peer_property give a client (cn_nonce 3,
+ * the READY's nonce as cn_peer_nonce) */
+int cz_connector_session(const cz_connector *c, int32_t slot, uint8_t precom[32], uint64_t *cn_nonce,
+                         uint64_t *cn_peer_nonce);
+int cz_connector_peer_property(const cz_connector *c, int32_t slot, const char *name, const uint8_t **value,
+                               uint32_t *len);
+/* cz_hs_error_status for a slot: the status code (300..500) of a well-formed ERROR it received, else 0 */
+int cz_connector_error_status(const cz_connector *c, int32_t slot);
+/* the server key a slot in use was dialled with */
+int cz_connector_server_key(const cz_connector *c, int32_t slot, uint8_t key[32]);
+/* as cz_engine_add_session: returns the connection id */
+int cz_engine_add_connected(cz_engine *e, const cz_connector *c, int32_t slot);
+/* wipe the slot's secrets (host and device) and free it for reuse */
+int cz_connector_release(cz_connector *c, int32_t slot);
+/* slots in use (handed out by stage 1 and not yet released) */
+uint32_t cz_connector_pending(const cz_connector *c);
+
 /* ---- 6. misc -------------------------------------------------------------- */
 const char *cz_last_error(void);
 const char *cz_version(void);

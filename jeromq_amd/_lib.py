@@ -184,6 +184,19 @@ SIGNATURES = {
     "cz_engine_add_accepted": (_I, [_VP, _VP, ctypes.c_int32]),
     "cz_acceptor_release": (_I, [_VP, ctypes.c_int32]),
     "cz_acceptor_pending": (_U32, [_VP]),
+    "cz_connector_create": (_I, [ctypes.POINTER(_VP), _VP, _VP, _I, _VP, _U32, _U32, _I]),
+    "cz_connector_destroy": (None, [_VP]),
+    "cz_connector_hello": (_I, [_VP, _U32, _VP, _VP, _U64, _VP, _VP]),
+    "cz_connector_welcome": (_I, [_VP, _U32, _VP, _VP, _U64, _VP, _VP, _VP, _U64, _VP, _VP]),
+    "cz_connector_ready": (_I, [_VP, _U32, _VP, _VP, _U64, _VP, _VP, _VP]),
+    "cz_connector_session": (_I, [_VP, ctypes.c_int32, _VP, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "cz_connector_peer_property": (_I, [_VP, ctypes.c_int32, ctypes.c_char_p, ctypes.POINTER(_VP),
+                                        ctypes.POINTER(_U32)]),
+    "cz_connector_error_status": (_I, [_VP, ctypes.c_int32]),
+    "cz_connector_server_key": (_I, [_VP, ctypes.c_int32, _VP]),
+    "cz_engine_add_connected": (_I, [_VP, _VP, ctypes.c_int32]),
+    "cz_connector_release": (_I, [_VP, ctypes.c_int32]),
+    "cz_connector_pending": (_U32, [_VP]),
     "cz_zmtp_metadata_check": (_I, [_VP, _U64, _I]),
     "cz_zmtp_metadata": (_U32, [_I, _VP, _U32, _VP, _U32]),
     "cz_last_error": (ctypes.c_char_p, []),

@@ -45,125 +45,9 @@ enum State {
 
 }  // namespace
 
-// Shared with the batched acceptor (cz_acceptor.cpp) through cz_internal.h.
+// Shared with the batched acceptor and connector through cz_internal.h; the host-only parsers (command
+// names, framing checks, the ERROR command, the metadata block) are in cz_hs_parse.cpp.
 namespace czi {
-
-// zmq/socket/Sockets.java: names by ZMQ_* type (the enum ordinal) and their compatible peers
-namespace {
-struct SockType {
-    const char *name;
-    const char *peers[3];
-};
-const SockType SOCK_TYPES[] = {
-    {"PAIR", {"PAIR"}},          {"PUB", {"SUB", "XSUB"}},       {"SUB", {"PUB", "XPUB"}},
-    {"REQ", {"REP", "ROUTER"}},  {"REP", {"REQ", "DEALER"}},     {"DEALER", {"REP", "DEALER", "ROUTER"}},
-    {"ROUTER", {"REQ", "DEALER", "ROUTER"}}, {"PULL", {"PUSH"}}, {"PUSH", {"PULL"}},
-    {"XPUB", {"SUB", "XSUB"}},   {"XSUB", {"PUB", "XPUB"}},      {"STREAM", {}},
-    {"SERVER", {"CLIENT"}},      {"CLIENT", {"SERVER"}},         {"RADIO", {"DISH"}},
-    {"DISH", {"RADIO"}},         {"CHANNEL", {"CHANNEL"}},       {"PEER", {"PEER"}},
-    {"RAW", {}},                 {"SCATTER", {"GATHER"}},        {"GATHER", {"SCATTER"}},
-};
-constexpr int NSOCK = (int)(sizeof(SOCK_TYPES) / sizeof(SOCK_TYPES[0]));
-constexpr int ZMQ_REQ = 3, ZMQ_DEALER = 5, ZMQ_ROUTER = 6;
-}  // namespace
-
-int sock_types() { return NSOCK; }
-
-bool compatible(int self, const std::string &peer)
-{
-    if (self < 0 || self >= NSOCK)
-        return false;
-    for (const char *p : SOCK_TYPES[self].peers)
-        if (p && peer == p)
-            return true;
-    return false;
-}
-
-// Msgs.startsWith(msg, data, true): the length byte, then bytes 1..len-1 against data[0..len-2]
-// (the loop never reaches the last character: the reference's quirk, mirrored)
-bool starts_with(const uint8_t *m, uint64_t size, const char *data)
-{
-    const uint64_t len = strlen(data);
-    if (size < len + 1 || m[0] != len)
-        return false;
-    for (uint64_t i = 1; i < len; i++)
-        if (m[i] != (uint8_t)data[i - 1])
-            return false;
-    return true;
-}
-
-uint64_t get_be64(const uint8_t *p)
-{
-    uint64_t v = 0;
-    for (int i = 0; i < 8; i++)
-        v = (v << 8) | p[i];
-    return v;
-}
-
-void put_be64(uint8_t *p, uint64_t v)
-{
-    for (int i = 7; i >= 0; i--, v >>= 8)
-        p[i] = (uint8_t)v;
-}
-
-// Mechanism.addProperty: name length byte, name, BE32 value length, value
-void add_property(std::vector<uint8_t> &b, const char *name, const uint8_t *value, uint32_t vlen)
-{
-    const size_t n = strlen(name);
-    b.push_back((uint8_t)n);
-    b.insert(b.end(), name, name + n);
-    for (int s = 24; s >= 0; s -= 8)
-        b.push_back((uint8_t)(vlen >> s));
-    if (vlen)
-        b.insert(b.end(), value, value + vlen);
-}
-
-// Metadata.read + Mechanism.parseMetadata's listener: CZ_OK, CZ_EPROTO (trailing bytes that are not
-// a whole property) or CZ_EINVAL (a Socket-Type the local type is not compatible with)
-int parse_metadata(const uint8_t *buf, uint64_t len, int self_type, Props *out)
-{
-    uint64_t left = len, i = 0;
-    while (left > 1) {
-        const uint32_t nl = buf[i];
-        if (nl == 0)
-            break;
-        i++;
-        left--;
-        if (left < nl)
-            break;
-        std::string name((const char *)buf + i, nl);
-        i += nl;
-        left -= nl;
-        if (left < 4)
-            break;
-        const int32_t vl = (int32_t)(((uint32_t)buf[i] << 24) | ((uint32_t)buf[i + 1] << 16) |
-                                     ((uint32_t)buf[i + 2] << 8) | buf[i + 3]);
-        i += 4;
-        left -= 4;
-        if (vl < 0 || left < (uint64_t)vl)
-            break;
-        std::string value((const char *)buf + i, (size_t)vl);
-        if (name == "Socket-Type" && !compatible(self_type, value))
-            return CZ_EINVAL;
-        if (out)
-            out->push_back({name, std::vector<uint8_t>(buf + i, buf + i + vl)});
-        i += (uint64_t)vl;
-        left -= (uint64_t)vl;
-    }
-    return left > 0 ? CZ_EPROTO : CZ_OK;
-}
-
-// the metadata block a socket of this type sends in INITIATE / READY: Socket-Type and, for REQ / DEALER /
-// ROUTER, Identity
-std::vector<uint8_t> zmtp_metadata(int socket_type, const uint8_t *identity, size_t identity_len)
-{
-    std::vector<uint8_t> b;
-    const char *tn = socket_type >= 0 && socket_type < NSOCK ? SOCK_TYPES[socket_type].name : "";
-    add_property(b, "Socket-Type", (const uint8_t *)tn, (uint32_t)strlen(tn));
-    if (socket_type == ZMQ_REQ || socket_type == ZMQ_DEALER || socket_type == ZMQ_ROUTER)
-        add_property(b, "Identity", identity, (uint32_t)identity_len);
-    return b;
-}
 
 // Wipe secret bytes with stores the compiler may not drop (a memset just before delete or a
 // return is a dead store it is allowed to remove).
@@ -273,8 +157,8 @@ struct cz_hs {
 
     int process_welcome(const uint8_t *m, uint64_t size)
     {
-        if (size != 168)
-            return proto(CZ_ZMTP_MALFORMED_COMMAND_READY);  // sic: the reference's event for a bad WELCOME
+        if (const int ev = welcome_framing(size))
+            return proto(ev);
         std::vector<uint8_t> c(16 + 144, 0), p(c.size());
         memcpy(c.data() + 16, m + 24, 144);
         uint8_t nonce[24];
@@ -332,11 +216,9 @@ struct cz_hs {
 
     int process_ready(const uint8_t *m, uint64_t size)
     {
-        if (size < 30)
-            return proto(CZ_ZMTP_MALFORMED_COMMAND_READY);
+        if (const int ev = ready_framing(size))
+            return proto(ev);
         const uint64_t clen = 16 + size - 14;
-        if (clen > 16 + 16 + 256)  // the reference's readyBox capacity (it would throw)
-            return proto(CZ_ZMTP_MALFORMED_COMMAND_READY);
         std::vector<uint8_t> c(clen, 0), p(clen);
         memcpy(c.data() + 16, m + 14, size - 14);
         uint8_t nonce[24];
@@ -357,25 +239,7 @@ struct cz_hs {
         if (state != EXPECT_WELCOME && state != EXPECT_READY)
             return proto(CZ_ZMTP_UNEXPECTED_COMMAND);
         state = ERROR_RECEIVED;
-        // Mechanism.parseErrorMessage
-        if (size < 7 && size != 6)
-            return proto(CZ_ZMTP_MALFORMED_COMMAND_ERROR);
-        if (size >= 7) {
-            const int8_t reason_len = (int8_t)m[6];  // a Java byte
-            if (reason_len > (int64_t)size - 7)
-                return proto(CZ_ZMTP_MALFORMED_COMMAND_ERROR);
-            if (size == 10) {
-                // handleErrorReason: "3xx".."5xx" with "00" -> handshake-failed-auth event
-                const char a = (char)m[7], b = (char)m[8], d = (char)m[9];
-                if (b == '0' && d == '0' && a >= '3' && a <= '5') {
-                    auth_status = (a - '0') * 100;
-                } else {
-                    event = CZ_ZAP_MALFORMED_REPLY;
-                    return CZ_EPROTO;
-                }
-            }
-        }
-        return CZ_OK;
+        return parse_error_command(m, size, &auth_status, &event);
     }
 
     // ---- server ----
@@ -571,13 +435,16 @@ struct cz_hs {
             // WELCOME would be opened under the all-zero cn_precom (a key anyone can compute) and
             // move the client to CONNECTED, and a WELCOME after CONNECTED would re-key the session.
             // So WELCOME is accepted only in EXPECT_WELCOME and READY only in EXPECT_READY.
-            if (size >= 8 && starts_with(m, size, "WELCOME"))
+            switch (client_command(m, size)) {
+            case CLIENT_CMD_WELCOME:
                 return state == EXPECT_WELCOME ? process_welcome(m, size) : proto(CZ_ZMTP_UNEXPECTED_COMMAND);
-            if (size >= 6 && starts_with(m, size, "READY"))
+            case CLIENT_CMD_READY:
                 return state == EXPECT_READY ? process_ready(m, size) : proto(CZ_ZMTP_UNEXPECTED_COMMAND);
-            if (size >= 6 && starts_with(m, size, "ERROR"))
+            case CLIENT_CMD_ERROR:
                 return process_error(m, size);
-            return proto(CZ_ZMTP_UNEXPECTED_COMMAND);
+            default:
+                return proto(CZ_ZMTP_UNEXPECTED_COMMAND);
+            }
         }
         switch (state) {
         case EXPECT_HELLO: return process_hello(m, size);
@@ -608,7 +475,7 @@ int cz_hs_create(cz_hs **out, int as_server, const uint8_t public_key[32], const
     if (!secret_key || (!as_server && (!public_key || !server_key)) || (identity_len && !identity) ||
         (entropy_len && !entropy))
         return fail(CZ_EINVAL, "cz_hs_create: missing key");
-    if (socket_type < 0 || socket_type >= NSOCK)
+    if (socket_type < 0 || socket_type >= sock_types())
         return fail(CZ_EINVAL, "cz_hs_create: unknown socket type %d", socket_type);
     cz_hs *h = new cz_hs();
     h->server = as_server != 0;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/curvezmq_mi355x.h"
+#include "cz_hs_parse.h"
 
 extern "C" {
 hipError_t czk_seal_desc(const cz_frame_desc *, const uint32_t *, uint32_t, const void *, void *, const void *,
@@ -93,15 +94,7 @@ struct HostBuf {
     void release();
 };
 
-// ---- ZMTP handshake helpers shared by cz_hs and cz_acceptor (defined in cz_curve_hs.cpp) ----
-typedef std::vector<std::pair<std::string, std::vector<uint8_t>>> Props;
-int sock_types();  // number of ZMQ_* socket types (valid types are 0 .. sock_types() - 1)
-bool starts_with(const uint8_t *m, uint64_t size, const char *data);  // Msgs.startsWith(msg, data, true)
-uint64_t get_be64(const uint8_t *p);
-void put_be64(uint8_t *p, uint64_t v);
-// Metadata.read + Mechanism.parseMetadata's Socket-Type check: CZ_OK / CZ_EPROTO / CZ_EINVAL
-int parse_metadata(const uint8_t *buf, uint64_t len, int self_type, Props *out);
-std::vector<uint8_t> zmtp_metadata(int socket_type, const uint8_t *identity, size_t identity_len);
+// (the handshake parsers shared by cz_hs, cz_acceptor and cz_connector: cz_hs_parse.h)
 void secure_wipe(void *p, size_t n);
 void secure_wipe(std::vector<uint8_t> &v);
 

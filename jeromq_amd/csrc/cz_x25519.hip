@@ -20,6 +20,7 @@
 
 #include "cz_fe25519.h"
 #include "cz_accept_kernels.h"  // the batched server handshake's kernels: the same ladder, one code object
+#include "cz_connect_kernels.h"  // the batched client handshake's, on the acceptor's box helpers
 
 namespace {
 

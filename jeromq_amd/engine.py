@@ -51,6 +51,13 @@ class CurveBatchEngine:
             _lib.check(rc, "cz_engine_add_accepted")
         return rc
 
+    def add_connected(self, connector, slot):
+        """A connection from a slot the batched connector (jeromq_amd.connector) has connected."""
+        rc = self._L.cz_engine_add_connected(self._h, connector._h, slot)
+        if rc < 0:
+            _lib.check(rc, "cz_engine_add_connected")
+        return rc
+
     def add_connection(self, precom, as_server=False, cn_nonce=None, cn_peer_nonce=None):
         """Per-connection CURVE state after the handshake: client MESSAGEs start at nonce 3
         and expect the server's from 2 (cn_peer_nonce 1); the server the other way round."""

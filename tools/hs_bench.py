@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Latency of the batched CURVE server handshake (cz_acceptor) against the per-connection one (cz_hs).
+"""Latency of the batched CURVE handshake (cz_acceptor, or cz_connector with --side client) against the
+per-connection one (cz_hs).
 
 For N in {1, 64, 1024, 16384, 131072}: wall clock around the synchronous cz_acceptor_hello (stage 1)
 and cz_acceptor_initiate (stage 2) calls, after one warm-up round, median of --reps rounds.  The
@@ -13,7 +14,12 @@ WELCOMEs (hence the INITIATEs made from them) are the same every round.  The dev
 does not depend on that.  `stage1_getrandom_ms` is stage 1 drawing its secrets and entropy from
 getrandom, as in production.
 
-Writes one JSON (default profiles/hs_batch/hs_batch.json) and prints it."""
+--side client times the three cz_connector stages (hello, welcome, ready) the same way: the server's
+WELCOMEs and READYs come from the CPU model, outside the timed region, for the injected short-term
+secrets and vouch nonces of POOL connections of one client; the baseline is 64 cz_hs clients one after
+another, constructor through READY.  `hello_getrandom_ms` is stage 1 drawing its secrets from getrandom.
+
+Writes one JSON (default profiles/hs_batch/hs_batch.json, or hs_connect.json for the client) and prints it."""
 import argparse
 import ctypes
 import json
@@ -122,14 +128,162 @@ def serial_baseline(pool, reps):
     return times[1:]
 
 
+def make_client_pool():
+    """POOL connections of one client (pool[0]'s long-term pair) to the one server"""
+    import hs_model as M
+    pool = make_pool()
+    cpub, csec = pool[0]["cpub"], pool[0]["csec"]
+    for c in pool:
+        c["initiate"] = M.client_initiate(c["welcome"], cpub, csec, SERVER_PUB, c["ceph"], c["vnonce"])
+        _, state = M.server_welcome(c["hello"], SERVER_SEC, c["seph"], c["entropy"])
+        c["ready"], _ = M.server_ready(c["initiate"], state)
+    return pool, cpub, csec
+
+
+class ClientBatch:
+    """prebuilt arguments of the three connector stage calls for n connections"""
+
+    def __init__(self, pool, n):
+        from jeromq_amd import _lib
+        self.n = n
+        idx = np.arange(n) % POOL
+
+        def rows(key, width):
+            return np.frombuffer(b"".join(c[key] for c in pool), dtype=np.uint8).reshape(POOL, width)[idx].copy()
+
+        self.rsize = len(pool[0]["ready"])
+        assert all(len(c["ready"]) == self.rsize for c in pool)
+        self.keys = np.frombuffer(SERVER_PUB * n, dtype=np.uint8).copy()
+        self.secrets, self.vnonces = rows("ceph", 32), rows("vnonce", 16)
+        self.welcomes, self.readys = rows("welcome", 168), rows("ready", self.rsize)
+        self.woff = np.arange(n, dtype=np.uint64) * np.uint64(168)
+        self.wsize = np.full(n, 168, dtype=np.uint32)
+        self.roff = np.arange(n, dtype=np.uint64) * np.uint64(self.rsize)
+        self.rsz = np.full(n, self.rsize, dtype=np.uint32)
+        self.res = (_lib.cz_accept_result * n)()
+        self.reply = np.zeros(n * 513, dtype=np.uint8)
+        self.slots = np.zeros(n, dtype=np.int32)
+        self.hello0, self.initiate0 = pool[0]["hello"], pool[0]["initiate"]
+
+    def _results(self, reply_len, what):
+        r = np.frombuffer(self.res, dtype=np.int32).reshape(self.n, 4)
+        assert not r[:, 0].any() and not r[:, 1].any() and (r[:, 3] == reply_len).all(), what
+        return r
+
+    def hello(self, L, con, injected=True):
+        t0 = time.perf_counter()
+        rc = L.cz_connector_hello(con, self.n, self.keys.ctypes.data, self.reply.ctypes.data, 200, self.res,
+                                  self.secrets.ctypes.data if injected else None)
+        dt = time.perf_counter() - t0
+        assert rc == 0, rc
+        self.slots[:] = self._results(200, "stage 1 gave no HELLO")[:, 2]
+        if injected:
+            assert self.reply[:200].tobytes() == self.hello0, "HELLO 0 differs from the model's"
+        return dt
+
+    def welcome(self, L, con):
+        t0 = time.perf_counter()
+        rc = L.cz_connector_welcome(con, self.n, self.slots.ctypes.data, self.welcomes.ctypes.data, self.welcomes.nbytes,
+                                    self.woff.ctypes.data, self.wsize.ctypes.data, self.reply.ctypes.data, 513, self.res,
+                                    self.vnonces.ctypes.data)
+        dt = time.perf_counter() - t0
+        assert rc == 0, rc
+        self._results(len(self.initiate0), "stage 2 refused a WELCOME")
+        assert self.reply[:len(self.initiate0)].tobytes() == self.initiate0, "INITIATE 0 differs from the model's"
+        return dt
+
+    def ready(self, L, con):
+        t0 = time.perf_counter()
+        rc = L.cz_connector_ready(con, self.n, self.slots.ctypes.data, self.readys.ctypes.data, self.readys.nbytes,
+                                  self.roff.ctypes.data, self.rsz.ctypes.data, self.res)
+        dt = time.perf_counter() - t0
+        assert rc == 0, rc
+        self._results(0, "stage 3 refused a READY")
+        return dt
+
+    def release(self, L, con):
+        for s in self.slots.tolist():
+            L.cz_connector_release(con, s)
+        assert L.cz_connector_pending(con) == 0
+
+
+def serial_client_baseline(pool, cpub, csec, reps):
+    """64 cz_hs clients, one after another, constructor through READY; seconds per round"""
+    from jeromq_amd import handshake
+    times = []
+    for _ in range(reps + 1):
+        t0 = time.perf_counter()
+        for c in pool:
+            cli = handshake.CurveClientHandshake(cpub, csec, SERVER_PUB, ephemeral_secret=c["ceph"], entropy=c["vnonce"])
+            rc, h = cli.nextHandshakeCommand()
+            assert cli.processHandshakeCommand(c["welcome"]) == 0
+            rc, ini = cli.nextHandshakeCommand()
+            assert cli.processHandshakeCommand(c["ready"]) == 0 and cli.status() == handshake.Status.READY
+            cli.close()
+        times.append(time.perf_counter() - t0)
+        assert ini.data == pool[-1]["initiate"]
+    return times[1:]
+
+
+def client_main(args):
+    import torch
+    from jeromq_amd import _lib
+    assert torch.cuda.is_available(), "hs_bench needs a GPU"
+    L = _lib.lib()
+    pool, cpub, csec = make_client_pool()
+    out = {"device": torch.cuda.get_device_name(0), "side": "client", "reps": args.reps, "pool": POOL,
+           "clock": "time.perf_counter", "initiate_bytes": len(pool[0]["initiate"]), "batched": []}
+    base = serial_client_baseline(pool, cpub, csec, args.reps)
+    out["serial_cz_hs"] = {"connections": POOL, "round_ms": [round(t * 1e3, 3) for t in base],
+                           "median_round_ms": round(statistics.median(base) * 1e3, 3),
+                           "median_per_connection_ms": round(statistics.median(base) * 1e3 / POOL, 4)}
+    for n in args.sizes:
+        con = ctypes.c_void_p()
+        _lib.check(L.cz_connector_create(ctypes.byref(con), cpub, csec, 0, None, 0, n, 0), "cz_connector_create")
+        b = ClientBatch(pool, n)
+        t1, t2, t3, t1r = [], [], [], []
+        for rep in range(args.reps + 1):   # round 0 warms up (buffers grow, code objects load)
+            a = b.hello(L, con)
+            w = b.welcome(L, con)
+            r = b.ready(L, con)
+            b.release(L, con)
+            g = b.hello(L, con, injected=False)
+            b.release(L, con)
+            if rep:
+                t1.append(a)
+                t2.append(w)
+                t3.append(r)
+                t1r.append(g)
+        L.cz_connector_destroy(con)
+        ms = lambda v: round(statistics.median(v) * 1e3, 4)  # noqa: E731
+        row = {"n": n, "hello_ms": ms(t1), "welcome_ms": ms(t2), "ready_ms": ms(t3), "hello_getrandom_ms": ms(t1r),
+               "hello_all_ms": [round(t * 1e3, 4) for t in t1], "welcome_all_ms": [round(t * 1e3, 4) for t in t2],
+               "ready_all_ms": [round(t * 1e3, 4) for t in t3],
+               "per_connection_us": round(sum(statistics.median(t) for t in (t1, t2, t3)) * 1e6 / n, 3)}
+        out["batched"].append(row)
+        print(f"n={n}: hello {row['hello_ms']} ms, welcome {row['welcome_ms']} ms, ready {row['ready_ms']} ms",
+              file=sys.stderr)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--side", choices=("server", "client"), default="server")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", type=int, nargs="*", default=list(SIZES))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hs_batch", "hs_batch.json"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.reps < 5:
         ap.error("--reps must be at least 5")
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "hs_batch",
+                                "hs_connect.json" if args.side == "client" else "hs_batch.json")
+    if args.side == "client":
+        return client_main(args)
     import torch
     from jeromq_amd import _lib
     assert torch.cuda.is_available(), "hs_bench needs a GPU"
