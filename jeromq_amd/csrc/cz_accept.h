@@ -1,27 +1,12 @@
 // cz_accept.h -- records shared by the batched server handshake's kernels (cz_accept_kernels.h) and its
 // host side (cz_acceptor.cpp).  Every record is a multiple of 16 bytes and every field 4-byte
-// aligned: the kernels read and write whole dwords.
+// aligned: the kernels read and write whole dwords.  Key agreements are cza_job lanes of k_x25519_jobs
+// and the status words are the handshakes' common ones (cz_hs_records.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// one key agreement: out = X25519(scalar, point | 9) [-> HSalsa20(., 0^16)]; device addresses
-struct cza_job {
-    const uint8_t *scalar;
-    const uint8_t *point;   // unused with CZA_JOB_BASE
-    uint8_t *out;
-    const uint32_t *gate;   // NULL, or a status word: the job runs only if it is CZA_ST_OK
-    uint32_t flags;
-    uint32_t pad;
-};
-#define CZA_JOB_BASE 1u
-#define CZA_JOB_BEFORENM 2u
-
-// per-lane status words
-#define CZA_ST_OK 0u
-#define CZA_ST_CRYPTO 1u        // a box or the cookie did not open / the cookie is another connection's
-#define CZA_ST_KEY_EXCHANGE 3u  // the vouch names another short-term key
-#define CZA_ST_NOT_RUN 0xffffffffu
+#include "cz_hs_records.h"
 
 // slot state record (device table, one per pending connection): every field is a secret or binds one
 #define CZA_STATE 128
@@ -63,7 +48,6 @@ struct cza_job {
 #define CZA_OUT2_PLAIN 320       // INITIATE plaintext: C 32, vouch nonce 16, vouch box 80, metadata
 
 extern "C" {
-hipError_t czk_x25519_jobs(const cza_job *jobs, uint32_t count, hipStream_t s);
 hipError_t czk_acc_welcome(const void *in, const void *x, void *out, void *state, uint32_t count, hipStream_t s);
 hipError_t czk_acc_initiate(const void *in, void *out, const void *state, uint32_t count, hipStream_t s);
 hipError_t czk_acc_ready(void *out, const void *x, const void *in, const void *state, const void *meta,

@@ -5,13 +5,13 @@
 // Mirrors CurveServerMechanism.processHello :254-299, produceWelcome :301-358, processInitiate
 // :360-471, produceReady :473-507 and produceError :509-517 item by item (no ZAP handler configured);
 // the per-connection form of the same state machine is cz_curve_hs.cpp, whose metadata parser and
-// Socket-Type table this file shares (cz_internal.h).
+// Socket-Type table this file shares (cz_hs_parse.h).  The handle, the chain every stage runs and the
+// entry points the client side has too are in cz_hs_batch.h.
 //
-// Launch chain (one stream, one synchronisation per stage):
-//   stage 1: memset out | H2D jobs + records | k_x25519_jobs (3 lanes per connection: S' = s'.9,
-//            k1 = beforenm(C', s), cnPrecom = beforenm(C', s')) | k_acc_welcome | D2H out | wipe | sync
-//   stage 2: memset out | H2D jobs + records | k_acc_initiate | k_x25519_jobs (k3 = beforenm(C, s'),
-//            gated on 2a's status) | k_acc_ready | D2H out | wipe | sync
+// The stages' kernels, between the H2D copy and the D2H copy of that chain:
+//   stage 1: k_x25519_jobs (3 lanes per connection: S' = s'.9, k1 = beforenm(C', s), cnPrecom =
+//            beforenm(C', s')) | k_acc_welcome
+//   stage 2: k_acc_initiate | k_x25519_jobs (k3 = beforenm(C, s'), gated on 2a's status) | k_acc_ready
 // k1 serves the HELLO open and the WELCOME box; cnPrecom is computed in stage 1 so that stage 2 has
 // one ladder on its critical path, not two ("Batched server handshake").  No key agreement runs twice for
 // a connection.  The host side parses command framing before the launch and the metadata after it.
@@ -20,23 +20,23 @@
 // cz_acceptor_release / destroy wipes the record.  The staging that carried them (pinned host and
 // device, both directions) is wiped before a stage returns.  The cookie plaintext never leaves the
 // device's registers.
-#include <sys/random.h>
-
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "cz_accept.h"
-#include "cz_internal.h"
+#include "cz_hs_batch.h"
 
 using namespace czi;
 
 namespace {
 
-enum SlotState : uint8_t { SLOT_FREE, SLOT_EXPECT_INITIATE, SLOT_FAILED, SLOT_CONNECTED };
+enum : uint8_t { SLOT_EXPECT_INITIATE = SLOT_WAITING };
+
+const uint64_t NEXT_NONCE = 2;  // READY took cn_nonce 1
 
 struct Slot {
-    SlotState state = SLOT_FREE;
+    uint8_t state = SLOT_FREE;
     bool have_key = false;
     uint8_t client_key[32] = {};  // C, from an INITIATE whose boxes opened
     uint8_t precom[32] = {};      // cnPrecom, once CONNECTED
@@ -54,91 +54,13 @@ struct Slot {
     }
 };
 
-uint64_t up16(uint64_t n) { return (n + 15) & ~15ull; }
-
-int fill_random(uint8_t *out, size_t n)
-{
-    size_t got = 0;
-    while (got < n) {
-        ssize_t r = getrandom(out + got, n - got, 0);
-        if (r < 0)
-            return fail(CZ_EINVAL, "cz_acceptor: getrandom failed");
-        got += (size_t)r;
-    }
-    return CZ_OK;
-}
-
-// off[i] + size[i] inside [0, cmds_bytes) for every command
-bool commands_inside(uint32_t count, uint64_t cmds_bytes, const uint64_t *off, const uint32_t *size)
-{
-    for (uint32_t i = 0; i < count; i++)
-        if (off[i] > cmds_bytes || size[i] > cmds_bytes - off[i])
-            return false;
-    return true;
-}
-
 }  // namespace
 
-struct cz_acceptor {
-    int device = 0;
-    int socket_type = 0;
-    uint32_t max_pending = 0;
-    hipStream_t stream = nullptr;
-    std::vector<Slot> slots;
-    std::vector<int32_t> free_slots;  // handed out from the back
-    std::vector<uint8_t> meta;        // the metadata READY carries
-    DevBuf konst;                     // [0,32) the long-term secret s, [32, 32 + CZA_META_MAX) metadata
-    DevBuf state;                     // max_pending x CZA_STATE
-    DevBuf work;                      // a stage's jobs, records, key agreements and output
-    HostBuf h_in, h_out;              // pinned staging of the same
-    std::vector<uint32_t> item;       // lane -> index of its command in the caller's batch
+// konst: [0,32) the long-term secret s, [32, 32 + CZA_META_MAX) metadata; state: max_pending x CZA_STATE
+struct cz_acceptor : HsBatch<Slot> {
+    std::vector<uint8_t> meta;  // the metadata READY carries
 
-    ~cz_acceptor()
-    {
-        (void)hipSetDevice(device);
-        if (stream) {
-            if (konst.ptr)
-                (void)hipMemsetAsync(konst.ptr, 0, konst.cap, stream);
-            if (state.ptr)
-                (void)hipMemsetAsync(state.ptr, 0, state.cap, stream);
-            if (work.ptr)
-                (void)hipMemsetAsync(work.ptr, 0, work.cap, stream);
-            (void)hipStreamSynchronize(stream);
-            (void)hipStreamDestroy(stream);
-        }
-        if (h_in.ptr)
-            secure_wipe(h_in.ptr, h_in.cap);
-        if (h_out.ptr)
-            secure_wipe(h_out.ptr, h_out.cap);
-        for (Slot &s : slots)
-            s.wipe();
-        konst.release();
-        state.release();
-        work.release();
-        h_in.release();
-        h_out.release();
-    }
-
-    Slot *slot(int32_t id) { return id >= 0 && (uint32_t)id < max_pending ? &slots[(size_t)id] : nullptr; }
-    const Slot *slot(int32_t id) const { return id >= 0 && (uint32_t)id < max_pending ? &slots[(size_t)id] : nullptr; }
-
-    void free_slot(int32_t id)
-    {
-        slots[(size_t)id].wipe();
-        free_slots.push_back(id);
-    }
-
-    // Wipe what a stage staged (it carried s', cookie keys, k1, cnPrecom), also after an error.
-    void wipe_staging(uint64_t dev_bytes, uint64_t in_bytes, uint64_t out_bytes)
-    {
-        if (work.ptr && dev_bytes)
-            (void)hipMemsetAsync(work.ptr, 0, dev_bytes, stream);
-        (void)hipStreamSynchronize(stream);
-        if (h_in.ptr)
-            secure_wipe(h_in.ptr, in_bytes);
-        if (h_out.ptr)
-            secure_wipe(h_out.ptr, out_bytes);
-    }
+    cz_acceptor() : HsBatch<Slot>("cz_acceptor", CZA_STATE) {}
 };
 
 extern "C" {
@@ -162,32 +84,11 @@ int cz_acceptor_create(cz_acceptor **out, const uint8_t secret_key[32], int sock
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
         return fail(CZ_EHIP, "no HIP device available (the CURVE path runs only on the GPU)");
     cz_acceptor *a = new cz_acceptor();
-    a->device = device;
-    a->socket_type = socket_type;
-    a->max_pending = max_pending;
     a->meta = std::move(meta);
-    a->slots.resize(max_pending);
-    a->free_slots.reserve(max_pending);
-    for (uint32_t i = max_pending; i > 0; i--)
-        a->free_slots.push_back((int32_t)(i - 1));
     uint8_t k[32 + CZA_META_MAX] = {};
     memcpy(k, secret_key, 32);
     memcpy(k + 32, a->meta.data(), a->meta.size());
-    hipError_t e;
-    if ((e = hipSetDevice(device)) != hipSuccess ||
-        (e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking)) != hipSuccess ||
-        (e = a->konst.reserve(sizeof k)) != hipSuccess ||
-        (e = a->state.reserve((uint64_t)CZA_STATE * max_pending)) != hipSuccess ||
-        (e = hipMemsetAsync(a->state.ptr, 0, a->state.cap, a->stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(a->konst.ptr, k, sizeof k, hipMemcpyHostToDevice, a->stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(a->stream)) != hipSuccess) {
-        secure_wipe(k, sizeof k);
-        delete a;
-        return hip_fail(e, "cz_acceptor_create");
-    }
-    secure_wipe(k, sizeof k);
-    *out = a;
-    return CZ_OK;
+    return hs_create(out, a, "cz_acceptor_create", k, sizeof k, socket_type, max_pending, device);
 }
 
 void cz_acceptor_destroy(cz_acceptor *a) { delete a; }
@@ -229,103 +130,73 @@ int cz_acceptor_hello(cz_acceptor *a, uint32_t count, const uint8_t *cmds, uint6
     const uint32_t nj = (uint32_t)a->item.size();
     if (nj == 0)
         return CZ_OK;
-    auto give_back = [&]() {  // (a failed call hands out no slot; a record a lane may have written is wiped)
-        for (uint32_t j = 0; j < nj; j++) {
-            if (a->state.ptr)
-                (void)hipMemsetAsync((uint8_t *)a->state.ptr + (uint64_t)CZA_STATE * (uint32_t)res[a->item[j]].slot, 0,
-                                     CZA_STATE, a->stream);
-            a->free_slot(res[a->item[j]].slot);
-            res[a->item[j]].slot = -1;
-        }
-    };
-    // 2. one staging block: jobs | records, then the key agreements and the output on the device
-    const uint64_t jobs_b = up16(3ull * nj * sizeof(cza_job));
-    const uint64_t in_b = jobs_b + (uint64_t)CZA_IN1 * nj;
-    const uint64_t x_off = in_b, out_off = x_off + (uint64_t)CZA_X1 * nj;
-    const uint64_t out_b = (uint64_t)CZA_OUT1 * nj;
-    hipError_t e;
-    if ((e = hipSetDevice(a->device)) != hipSuccess || (e = a->work.reserve(out_off + out_b)) != hipSuccess ||
-        (e = a->h_in.reserve(in_b)) != hipSuccess || (e = a->h_out.reserve(out_b)) != hipSuccess) {
-        give_back();
-        return hip_fail(e, "cz_acceptor_hello: buffers");
-    }
-    uint8_t *h = (uint8_t *)a->h_in.ptr, *d = (uint8_t *)a->work.ptr;
+    // 2. the records, and three key agreements per record into x (the output is the WELCOME: no secret)
+    Stage<Slot> st(*a, "cz_acceptor_hello", nj, LaneShape{3, CZA_IN1, CZA_X1, CZA_OUT1}, false, res);
+    int rc = st.reserve();
+    if (rc != CZ_OK)
+        return rc;
+    const StageBuffers sb = st.buffers();
     const uint8_t *d_key = (const uint8_t *)a->konst.ptr;
-    cza_job *jobs = (cza_job *)h;  // (every byte the kernels read is written below: no blanket memset)
-    int rc = CZ_OK;
+    cza_job *jobs = sb.jobs;
     for (uint32_t j = 0; j < nj && rc == CZ_OK; j++) {
         const uint32_t i = a->item[j];
         const uint8_t *m = cmds + off[i];
-        uint8_t *r = h + jobs_b + (uint64_t)CZA_IN1 * j;
+        uint8_t *r = sb.recs + (uint64_t)CZA_IN1 * j;
         memcpy(r + CZA_IN1_CP, m + 80, 32);
         memcpy(r + CZA_IN1_NONCE, m + 112, 8);
         memcpy(r + CZA_IN1_BOX, m + 120, 80);
         static_assert(CZA_IN1_SECRET == CZA_IN1_ENTROPY + 64, "entropy and s' are drawn in one call");
         if (!test_entropy && !test_secrets) {
-            rc = fill_random(r + CZA_IN1_ENTROPY, 96);
+            rc = fill_random(r + CZA_IN1_ENTROPY, 96, a->name);
         } else {
             if (test_entropy)
                 memcpy(r + CZA_IN1_ENTROPY, test_entropy + 64ull * i, 64);
             else
-                rc = fill_random(r + CZA_IN1_ENTROPY, 64);
+                rc = fill_random(r + CZA_IN1_ENTROPY, 64, a->name);
             if (test_secrets)
                 memcpy(r + CZA_IN1_SECRET, test_secrets + 32ull * i, 32);
             else if (rc == CZ_OK)
-                rc = fill_random(r + CZA_IN1_SECRET, 32);
+                rc = fill_random(r + CZA_IN1_SECRET, 32, a->name);
         }
         const int32_t slot = res[i].slot;
         memcpy(r + CZA_IN1_SLOT, &slot, 4);
-        const uint8_t *dr = d + jobs_b + (uint64_t)CZA_IN1 * j;
-        uint8_t *dx = d + x_off + (uint64_t)CZA_X1 * j;
+        const uint8_t *dr = sb.d_recs + (uint64_t)CZA_IN1 * j;
+        uint8_t *dx = sb.d_x + (uint64_t)CZA_X1 * j;
         jobs[3 * j] = cza_job{dr + CZA_IN1_SECRET, nullptr, dx, nullptr, CZA_JOB_BASE, 0};                    // S'
         jobs[3 * j + 1] = cza_job{d_key, dr + CZA_IN1_CP, dx + 32, nullptr, CZA_JOB_BEFORENM, 0};             // k1
         jobs[3 * j + 2] = cza_job{dr + CZA_IN1_SECRET, dr + CZA_IN1_CP, dx + 64, nullptr, CZA_JOB_BEFORENM, 0};  // cnPrecom
     }
-    if (rc != CZ_OK) {
-        secure_wipe(h, in_b);
-        give_back();
+    if (rc != CZ_OK)
+        return st.abandon(rc);
+    rc = st.run([=](hipStream_t s) {
+        const hipError_t e = czk_x25519_jobs(sb.d_jobs, 3 * nj, s);
+        return e != hipSuccess ? e : czk_acc_welcome(sb.d_recs, sb.d_x, sb.d_out, a->state.ptr, nj, s);
+    });
+    if (rc != CZ_OK)
         return rc;
-    }
-    // 3. the launch chain and its one synchronisation
-    if ((e = hipMemsetAsync(d + out_off, 0xff, out_b, a->stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(d, h, in_b, hipMemcpyHostToDevice, a->stream)) != hipSuccess ||
-        (e = czk_x25519_jobs((const cza_job *)d, 3 * nj, a->stream)) != hipSuccess ||
-        (e = czk_acc_welcome(d + jobs_b, d + x_off, d + out_off, a->state.ptr, nj, a->stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(a->h_out.ptr, d + out_off, out_b, hipMemcpyDeviceToHost, a->stream)) != hipSuccess ||
-        (e = hipMemsetAsync(d, 0, out_off, a->stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(a->stream)) != hipSuccess) {
-        a->wipe_staging(out_off + out_b, in_b, out_b);
-        give_back();
-        return hip_fail(e, "cz_acceptor_hello");
-    }
     for (uint32_t j = 0; j < nj; j++)  // the staged secrets: cookie key and s' (the rest came off the wire)
-        secure_wipe(h + jobs_b + (uint64_t)CZA_IN1 * j + CZA_IN1_ENTROPY, 96);
-    // 4. results: WELCOME and a pending slot, or ERROR (processHello's failed open, produceError)
-    const uint8_t *ho = (const uint8_t *)a->h_out.ptr;
+        secure_wipe(sb.recs + (uint64_t)CZA_IN1 * j + CZA_IN1_ENTROPY, 96);
+    // 3. results: WELCOME and a pending slot, or ERROR (processHello's failed open, produceError)
     for (uint32_t j = 0; j < nj; j++) {
         const uint32_t i = a->item[j];
-        const uint8_t *o = ho + (uint64_t)CZA_OUT1 * j;
-        uint32_t st;
-        memcpy(&st, o + CZA_OUT1_STATUS, 4);
+        const uint8_t *o = sb.out + (uint64_t)CZA_OUT1 * j;
         uint8_t *rp = reply + reply_stride * i;
-        if (st == CZA_ST_OK) {
+        const uint32_t status = st.status(j, o + CZA_OUT1_STATUS, res[i]);
+        if (status == CZA_ST_OK) {
             memcpy(rp, o + CZA_OUT1_CMD, 168);
             res[i].reply_len = 168;
             a->slots[(size_t)res[i].slot].state = SLOT_EXPECT_INITIATE;
-        } else if (st == CZA_ST_CRYPTO) {
+            continue;
+        }
+        if (status == CZA_ST_CRYPTO) {
             memcpy(rp, "\x05" "ERROR\x00", 7);
             res[i].reply_len = 7;
             res[i].event = CZ_ZMTP_CRYPTOGRAPHIC;
-            a->free_slot(res[i].slot);
-            res[i].slot = -1;
-        } else {  // the lane did not run: a device failure the runtime did not report
-            a->free_slot(res[i].slot);
-            res[i].slot = -1;
-            res[i].rc = CZ_EHIP;
-            rc = fail(CZ_EHIP, "cz_acceptor_hello: lane %u left no status", j);
         }
+        a->free_slot(res[i].slot);
+        res[i].slot = -1;
     }
-    return rc;
+    return st.rc;
 }
 
 int cz_acceptor_initiate(cz_acceptor *a, uint32_t count, const int32_t *slot, const uint8_t *cmds, uint64_t cmds_bytes,
@@ -368,21 +239,18 @@ int cz_acceptor_initiate(cz_acceptor *a, uint32_t count, const int32_t *slot, co
     const uint32_t nj = (uint32_t)a->item.size();
     if (nj == 0)
         return CZ_OK;
-    const uint64_t jobs_b = up16((uint64_t)nj * sizeof(cza_job));
-    const uint64_t in_b = jobs_b + (uint64_t)CZA_IN2 * nj;
-    const uint64_t x_off = in_b, out_off = x_off + 32ull * nj;
-    const uint64_t out_b = (uint64_t)CZA_OUT2 * nj;
-    hipError_t e;
-    if ((e = hipSetDevice(a->device)) != hipSuccess || (e = a->work.reserve(out_off + out_b)) != hipSuccess ||
-        (e = a->h_in.reserve(in_b)) != hipSuccess || (e = a->h_out.reserve(out_b)) != hipSuccess)
-        return hip_fail(e, "cz_acceptor_initiate: buffers");
-    uint8_t *h = (uint8_t *)a->h_in.ptr, *d = (uint8_t *)a->work.ptr;
+    // 2. the records, and one key agreement per record into x (the output carries cnPrecom)
+    Stage<Slot> st(*a, "cz_acceptor_initiate", nj, LaneShape{1, CZA_IN2, 32, CZA_OUT2}, true, nullptr);
+    int rc = st.reserve();
+    if (rc != CZ_OK)
+        return rc;
+    const StageBuffers sb = st.buffers();
     const uint8_t *d_state = (const uint8_t *)a->state.ptr;
-    cza_job *jobs = (cza_job *)h;  // (every byte the kernels read is written below: no blanket memset)
+    cza_job *jobs = sb.jobs;
     for (uint32_t j = 0; j < nj; j++) {
         const uint32_t i = a->item[j];
         const uint8_t *m = cmds + off[i];
-        uint8_t *r = h + jobs_b + (uint64_t)CZA_IN2 * j;
+        uint8_t *r = sb.recs + (uint64_t)CZA_IN2 * j;
         const uint32_t plain_len = size[i] - 113 - 16;  // 128 .. CZA_INIT_MAX
         memcpy(r + CZA_IN2_SLOT, &slot[i], 4);
         memcpy(r + CZA_IN2_LEN, &plain_len, 4);
@@ -391,42 +259,33 @@ int cz_acceptor_initiate(cz_acceptor *a, uint32_t count, const int32_t *slot, co
         memcpy(r + CZA_IN2_COOKIE, m + 25, 80);
         memcpy(r + CZA_IN2_BOX, m + 113, size[i] - 113);
         memset(r + CZA_IN2_BOX + 16 + plain_len, 0, (0u - plain_len) & 15u);  // the last chunk's pad
-        uint8_t *dout = d + out_off + (uint64_t)CZA_OUT2 * j;
+        uint8_t *dout = sb.d_out + (uint64_t)CZA_OUT2 * j;
         // k3 = beforenm(C, s'): the vouch's key, once 2a has opened the box that holds C
         jobs[j] = cza_job{d_state + (uint64_t)CZA_STATE * (uint32_t)slot[i] + CZA_STATE_SECRET, dout + CZA_OUT2_PLAIN,
-                          d + x_off + 32ull * j, (const uint32_t *)(dout + CZA_OUT2_STATUS), CZA_JOB_BEFORENM, 0};
+                          sb.d_x + 32ull * j, (const uint32_t *)(dout + CZA_OUT2_STATUS), CZA_JOB_BEFORENM, 0};
     }
-    if ((e = hipMemsetAsync(d + out_off, 0xff, out_b, a->stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(d, h, in_b, hipMemcpyHostToDevice, a->stream)) != hipSuccess ||
-        (e = czk_acc_initiate(d + jobs_b, d + out_off, d_state, nj, a->stream)) != hipSuccess ||
-        (e = czk_x25519_jobs((const cza_job *)d, nj, a->stream)) != hipSuccess ||
-        (e = czk_acc_ready(d + out_off, d + x_off, d + jobs_b, d_state, (const uint8_t *)a->konst.ptr + 32,
-                           (uint32_t)a->meta.size(), nj, a->stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(a->h_out.ptr, d + out_off, out_b, hipMemcpyDeviceToHost, a->stream)) != hipSuccess ||
-        (e = hipMemsetAsync(d, 0, out_off + out_b, a->stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(a->stream)) != hipSuccess) {
-        a->wipe_staging(out_off + out_b, in_b, out_b);
-        return hip_fail(e, "cz_acceptor_initiate");
-    }
-    // 2. results: the metadata (Metadata.read + the Socket-Type check) on the host, then READY
-    int rc = CZ_OK;
-    const uint8_t *ho = (const uint8_t *)a->h_out.ptr;
+    rc = st.run([=](hipStream_t s) {
+        hipError_t e;
+        if ((e = czk_acc_initiate(sb.d_recs, sb.d_out, d_state, nj, s)) != hipSuccess ||
+            (e = czk_x25519_jobs(sb.d_jobs, nj, s)) != hipSuccess)
+            return e;
+        return czk_acc_ready(sb.d_out, sb.d_x, sb.d_recs, d_state, (const uint8_t *)a->konst.ptr + 32,
+                             (uint32_t)a->meta.size(), nj, s);
+    });
+    if (rc != CZ_OK)
+        return rc;
+    // 3. results: the metadata (Metadata.read + the Socket-Type check) on the host, then READY
     for (uint32_t j = 0; j < nj; j++) {
         const uint32_t i = a->item[j];
-        const uint8_t *o = ho + (uint64_t)CZA_OUT2 * j;
+        uint8_t *o = sb.out + (uint64_t)CZA_OUT2 * j;
         Slot &s = a->slots[(size_t)slot[i]];
-        uint32_t st;
-        memcpy(&st, o + CZA_OUT2_STATUS, 4);
-        if (st == CZA_ST_CRYPTO || st == CZA_ST_KEY_EXCHANGE) {
+        const uint32_t status = st.status(j, o + CZA_OUT2_STATUS, res[i], {CZA_ST_OK, CZA_ST_CRYPTO, CZA_ST_KEY_EXCHANGE});
+        if (status == CZA_ST_CRYPTO || status == CZA_ST_KEY_EXCHANGE) {
             res[i].rc = CZ_EPROTO;
-            res[i].event = st == CZA_ST_KEY_EXCHANGE ? CZ_ZMTP_KEY_EXCHANGE : CZ_ZMTP_CRYPTOGRAPHIC;
-            continue;
+            res[i].event = status == CZA_ST_KEY_EXCHANGE ? CZ_ZMTP_KEY_EXCHANGE : CZ_ZMTP_CRYPTOGRAPHIC;
         }
-        if (st != CZA_ST_OK) {  // the lane did not run: a device failure the runtime did not report
-            res[i].rc = CZ_EHIP;
-            rc = fail(CZ_EHIP, "cz_acceptor_initiate: lane %u left no status", j);
+        if (status != CZA_ST_OK)
             continue;
-        }
         const uint8_t *m = cmds + off[i];
         const uint32_t plain_len = size[i] - 113 - 16;
         memcpy(s.client_key, o + CZA_OUT2_PLAIN, 32);
@@ -438,12 +297,12 @@ int cz_acceptor_initiate(cz_acceptor *a, uint32_t count, const int32_t *slot, co
             continue;
         }
         memcpy(s.precom, o + CZA_OUT2_PRECOM, 32);
-        secure_wipe((uint8_t *)a->h_out.ptr + (uint64_t)CZA_OUT2 * j + CZA_OUT2_PRECOM, 32);
+        secure_wipe(o + CZA_OUT2_PRECOM, 32);
         s.peer_nonce = get_be64(m + 105);
         s.state = SLOT_CONNECTED;
         uint8_t *rp = reply + reply_stride * i;
         memcpy(rp, "\x05READY", 6);
-        put_be64(rp + 6, 1);  // cn_nonce = 1; the session continues at 2
+        put_be64(rp + 6, 1);  // cn_nonce = 1; the session continues at NEXT_NONCE
         memcpy(rp + 14, o + CZA_OUT2_READY, 16 + a->meta.size());
         res[i].reply_len = (uint32_t)(14 + 16 + a->meta.size());
     }
@@ -451,22 +310,14 @@ int cz_acceptor_initiate(cz_acceptor *a, uint32_t count, const int32_t *slot, co
     // for lanes whose metadata failed, wiped here)
     for (uint32_t j = 0; j < nj; j++)
         if (a->slots[(size_t)slot[a->item[j]]].state != SLOT_CONNECTED)
-            secure_wipe((uint8_t *)a->h_out.ptr + (uint64_t)CZA_OUT2 * j + CZA_OUT2_PRECOM, 32);
-    return rc;
+            secure_wipe(sb.out + (uint64_t)CZA_OUT2 * j + CZA_OUT2_PRECOM, 32);
+    return st.rc;
 }
 
 int cz_acceptor_session(const cz_acceptor *a, int32_t slot, uint8_t precom[32], uint64_t *cn_nonce,
                         uint64_t *cn_peer_nonce)
 {
-    if (!a || !precom || !cn_nonce || !cn_peer_nonce)
-        return fail(CZ_EINVAL, "cz_acceptor_session: null pointer");
-    const Slot *s = a->slot(slot);
-    if (!s || s->state != SLOT_CONNECTED)
-        return fail(CZ_EINVAL, "cz_acceptor_session: slot %d has no completed handshake", slot);
-    memcpy(precom, s->precom, 32);
-    *cn_nonce = 2;
-    *cn_peer_nonce = s->peer_nonce;
-    return CZ_OK;
+    return hs_session(a, "cz_acceptor_session", slot, precom, cn_nonce, cn_peer_nonce, NEXT_NONCE);
 }
 
 int cz_acceptor_client_key(const cz_acceptor *a, int32_t slot, uint8_t key[32])
@@ -480,50 +331,17 @@ int cz_acceptor_client_key(const cz_acceptor *a, int32_t slot, uint8_t key[32])
 
 int cz_acceptor_peer_property(const cz_acceptor *a, int32_t slot, const char *name, const uint8_t **value, uint32_t *len)
 {
-    if (!a || !name || !value || !len)
-        return fail(CZ_EINVAL, "cz_acceptor_peer_property: null pointer");
-    const Slot *s = a->slot(slot);
-    if (s && s->state != SLOT_FREE)
-        for (const auto &p : s->peer)
-            if (p.first == name) {
-                *value = p.second.data();
-                *len = (uint32_t)p.second.size();
-                return CZ_OK;
-            }
-    return fail(CZ_EINVAL, "cz_acceptor_peer_property: no property %s on slot %d", name, slot);
+    return hs_peer_property(a, "cz_acceptor_peer_property", slot, name, value, len);
 }
 
 int cz_engine_add_accepted(cz_engine *e, const cz_acceptor *a, int32_t slot)
 {
-    uint8_t k[32];
-    uint64_t n, pn;
-    int rc = cz_acceptor_session(a, slot, k, &n, &pn);
-    if (rc != CZ_OK)
-        return rc;
-    rc = cz_engine_add_conn(e, 1, k, n, pn);
-    secure_wipe(k, 32);
-    return rc;
+    return hs_engine_add(e, a, "cz_acceptor_session", slot, NEXT_NONCE, 1);
 }
 
-int cz_acceptor_release(cz_acceptor *a, int32_t slot)
-{
-    Slot *s = a ? a->slot(slot) : nullptr;
-    if (!s || s->state == SLOT_FREE)
-        return fail(CZ_EINVAL, "cz_acceptor_release: slot %d is not in use", slot);
-    // the device record (s', cookie key, cnPrecom): wiped in stream order, so before any later stage
-    // can hand the slot to another connection; cz_acceptor_destroy waits for it
-    hipError_t e;
-    if ((e = hipSetDevice(a->device)) != hipSuccess ||
-        (e = hipMemsetAsync((uint8_t *)a->state.ptr + (uint64_t)CZA_STATE * (uint32_t)slot, 0, CZA_STATE, a->stream)) !=
-            hipSuccess)
-        return hip_fail(e, "cz_acceptor_release");
-    a->free_slot(slot);
-    return CZ_OK;
-}
+// (the device record holds s', the cookie key and cnPrecom)
+int cz_acceptor_release(cz_acceptor *a, int32_t slot) { return hs_release(a, "cz_acceptor_release", slot); }
 
-uint32_t cz_acceptor_pending(const cz_acceptor *a)
-{
-    return a ? a->max_pending - (uint32_t)a->free_slots.size() : 0;
-}
+uint32_t cz_acceptor_pending(const cz_acceptor *a) { return hs_pending(a); }
 
 }  // extern "C"

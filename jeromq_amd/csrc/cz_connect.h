@@ -1,12 +1,12 @@
 // cz_connect.h -- records shared by the batched client handshake's kernels (cz_connect_kernels.h) and
-// its host side (cz_connector.cpp).  As in cz_accept.h every record is a multiple of 16 bytes and
-// every field 4-byte aligned: the kernels read and write whole dwords.  Key agreements are cza_job
-// lanes of k_x25519_jobs and the status words are the acceptor's (cz_accept.h).
+// its host side (cz_connector.cpp).  Every record is a multiple of 16 bytes and every field 4-byte
+// aligned: the kernels read and write whole dwords.  Key agreements are cza_job lanes of k_x25519_jobs
+// and the status words are the handshakes' common ones (cz_hs_records.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "cz_accept.h"
+#include "cz_hs_records.h"
 
 // slot state record (device table, one per pending connection): every field is a secret
 #define CZC_STATE 128

@@ -1,7 +1,7 @@
 // cz_connect_kernels.h -- device side of the batched CURVE client handshake (cz_connector, section 12
 // of the header): HELLO, WELCOME -> INITIATE and READY for many connections per launch.  Compiled as
-// part of cz_x25519.hip after cz_accept_kernels.h, whose helpers (xs_fixed, xs_mem, ldw, diff, w4,
-// wipe_words) and whose per-lane-job X25519 kernel it uses: one code object, one copy of the ladder.
+// part of cz_x25519.hip, the handshake's device translation unit, on the box helpers and the
+// per-lane-job X25519 kernel of cz_hs_dev.h.
 //
 // Reference: CurveClientMechanism.produceHello :246-279, processWelcome :281-316, produceInitiate
 // :318-385, processReady :387-419.  Per connection the reference runs, through Curve.box / open /
@@ -13,16 +13,13 @@
 //   k_con_initiate  stage 2b: seal the vouch under kV and the INITIATE box under cnPrecom, write the
 //                   command, wipe c', kH and kV from the slot;
 //   k_con_ready     stage 3: open the READY box under cnPrecom.
-// NaCl's rules as in the acceptor's kernels: tags are compared without an early exit; a failed open
-// leaves no plaintext behind; a lane whose check fails writes its status and returns, and its
-// neighbours in the wave carry on.  Every lane reads and writes its own 4-byte-aligned records with
-// dword accesses.
+// NaCl's rules and the access pattern: cz_hs_dev.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "cz_accept_kernels.h"
 #include "cz_connect.h"
+#include "cz_hs_dev.h"
 
 namespace {
 
@@ -216,39 +213,23 @@ extern "C" {
 
 hipError_t czk_con_hello(const void *in, const void *x, void *out, void *state, uint32_t count, hipStream_t s)
 {
-    if (count == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(k_con_hello, dim3((count + 63) / 64), dim3(64), 0, s, (const uint8_t *)in, (const uint8_t *)x,
-                       (uint8_t *)out, (uint8_t *)state, count);
-    return hipGetLastError();
+    return launch_lanes(k_con_hello, count, s, in, x, out, state, count);
 }
 
 hipError_t czk_con_welcome(const void *in, void *out, void *x, const void *state, uint32_t count, hipStream_t s)
 {
-    if (count == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(k_con_welcome, dim3((count + 63) / 64), dim3(64), 0, s, (const uint8_t *)in, (uint8_t *)out,
-                       (uint8_t *)x, (const uint8_t *)state, count);
-    return hipGetLastError();
+    return launch_lanes(k_con_welcome, count, s, in, out, x, state, count);
 }
 
 hipError_t czk_con_initiate(void *out, void *x, const void *in, void *state, const void *konst, uint32_t meta_len,
                             uint32_t count, hipStream_t s)
 {
-    if (count == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(k_con_initiate, dim3((count + 63) / 64), dim3(64), 0, s, (uint8_t *)out, (uint8_t *)x,
-                       (const uint8_t *)in, (uint8_t *)state, (const uint8_t *)konst, meta_len, count);
-    return hipGetLastError();
+    return launch_lanes(k_con_initiate, count, s, out, x, in, state, konst, meta_len, count);
 }
 
 hipError_t czk_con_ready(const void *in, void *out, const void *state, uint32_t count, hipStream_t s)
 {
-    if (count == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(k_con_ready, dim3((count + 63) / 64), dim3(64), 0, s, (const uint8_t *)in, (uint8_t *)out,
-                       (const uint8_t *)state, count);
-    return hipGetLastError();
+    return launch_lanes(k_con_ready, count, s, in, out, state, count);
 }
 
 }  // extern "C"

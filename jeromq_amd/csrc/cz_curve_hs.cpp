@@ -21,13 +21,12 @@
 // over 256 bytes) this returns CZ_EPROTO / CZ_EMSGSIZE instead.  ZAP (RFC 27) is out of scope
 // (SURVEY.md section 2): with zap enabled the server stops in EXPECT_ZAP_REPLY and the caller
 // supplies the status code (cz_hs_zap_reply), which is what zapMsgAvailable consumes.
-#include <sys/random.h>
-
 #include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
 
+#include "cz_hs_batch.h"  // fill_random
 #include "cz_internal.h"
 
 using namespace czi;
@@ -107,14 +106,7 @@ struct cz_hs {
             entropy_pos += n;
             return CZ_OK;
         }
-        size_t got = 0;
-        while (got < n) {
-            ssize_t r = getrandom(out + got, n - got, 0);
-            if (r < 0)
-                return fail(CZ_EINVAL, "cz_hs: getrandom failed");
-            got += (size_t)r;
-        }
-        return CZ_OK;
+        return fill_random(out, n, "cz_hs");
     }
 
     int proto(int ev)

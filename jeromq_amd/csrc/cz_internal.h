@@ -1,4 +1,5 @@
-// cz_internal.h -- shared host-side helpers of libcurvezmq_mi355x (not part of the C-ABI).
+// cz_internal.h -- shared host-side helpers of libcurvezmq_mi355x (not part of the C-ABI).  The handshake's
+// parsers are in cz_hs_parse.h, what the batched acceptor and connector share in cz_hs_batch.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>

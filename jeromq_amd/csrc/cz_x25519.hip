@@ -19,8 +19,9 @@
 #include <stdint.h>
 
 #include "cz_fe25519.h"
-#include "cz_accept_kernels.h"  // the batched server handshake's kernels: the same ladder, one code object
-#include "cz_connect_kernels.h"  // the batched client handshake's, on the acceptor's box helpers
+#include "cz_hs_dev.h"  // the batched handshakes' box helpers and k_x25519_jobs: the same ladder, one code object
+#include "cz_accept_kernels.h"   // the batched server handshake's kernels
+#include "cz_connect_kernels.h"  // the batched client handshake's
 
 namespace {
 
@@ -57,9 +58,5 @@ __global__ __launch_bounds__(64) void k_x25519(const uint8_t *__restrict__ scala
 extern "C" hipError_t czk_x25519(const void *scalars, const void *points, void *out, uint32_t count, int beforenm,
                                  hipStream_t s)
 {
-    if (count == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(k_x25519, dim3((count + 63) / 64), dim3(64), 0, s, (const uint8_t *)scalars,
-                       (const uint8_t *)points, (uint8_t *)out, count, beforenm);
-    return hipGetLastError();
+    return launch_lanes(k_x25519, count, s, scalars, points, out, count, beforenm);
 }
