@@ -134,3 +134,45 @@ def server_ready(initiate, state, socket_type=0, identity=b"", nonce=1):
     n8 = struct.pack(">Q", nonce)
     ready = b"\x05READY" + n8 + _seal(metadata(socket_type, identity), b"CurveZMQREADY---" + n8, state["precom"])
     return ready, {"client_key": client_key, "metadata": meta, "precom": state["precom"]}
+
+
+# ---- commands sealed under an agreed key ----------------------------------------------------
+# A peer that sends a point it holds no secret for (a steered, non-canonical or low-order key:
+# tests/hs_steer.py) cannot run X25519 on its side; the key both sides end at is known to the test,
+# and these build the peer's commands under that key directly.  Same layouts as above.
+def hello_under(k1, cli_eph, nonce=1, box=None):
+    """HELLO for the short-term key cli_eph, its box sealed under k1 (or `box`: 80 bytes as they are)"""
+    n8 = struct.pack(">Q", nonce)
+    if box is None:
+        box = _seal(bytes(64), b"CurveZMQHELLO---" + n8, k1)
+    assert len(box) == 80 and len(cli_eph) == 32
+    return b"\x05HELLO\x01\x00" + bytes(72) + bytes(cli_eph) + n8 + bytes(box)
+
+
+def welcome_under(k1, srv_eph, cookie96, wnonce):
+    """WELCOME: Box [S' + cookie nonce 16 + cookie 80] under k1"""
+    assert len(srv_eph) == 32 and len(cookie96) == 96 and len(wnonce) == 16
+    return b"\x07WELCOME" + bytes(wnonce) + _seal(bytes(srv_eph) + bytes(cookie96), b"WELCOME-" + bytes(wnonce), k1)
+
+
+def vouch_under(kv, vouch_nonce, cli_eph, server_key):
+    """the vouch Box [C' + S] under kv = beforenm(S', c)"""
+    return _seal(bytes(cli_eph) + bytes(server_key), b"VOUCH---" + bytes(vouch_nonce), kv)
+
+
+def initiate_under(cookie96, precom, plain, nonce=2, box=None):
+    """INITIATE: the cookie as received, Box [plain] under precom (or `box`: tag + ciphertext as they are);
+    plain = C + vouch nonce + vouch + metadata"""
+    n8 = struct.pack(">Q", nonce)
+    if box is None:
+        box = _seal(plain, b"CurveZMQINITIATE" + n8, precom)
+    assert len(cookie96) == 96
+    return b"\x08INITIATE" + bytes(cookie96) + n8 + bytes(box)
+
+
+def ready_under(precom, meta, nonce=1, box=None):
+    """READY: Box [metadata] under precom (or `box`: tag + ciphertext as they are)"""
+    n8 = struct.pack(">Q", nonce)
+    if box is None:
+        box = _seal(meta, b"CurveZMQREADY---" + n8, precom)
+    return b"\x05READY" + n8 + bytes(box)
