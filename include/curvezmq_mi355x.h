@@ -212,6 +212,33 @@ int cz_open_segments(const cz_frame_desc *d_desc, const cz_segment *d_seg, uint3
                      uint32_t ncomb, const void *d_in, void *d_out, const void *d_subkeys, void *d_work,
                      uint16_t *d_status, uint64_t *d_nonces, void *stream);
 
+/* ---- 3c. fan-out: one payload sealed for many connections ------------------------
+ * A PUB / XPUB socket hands the SAME Msg to every matching pipe (Dist.distribute,
+ * zmq/socket/pubsub/Dist.java -> write(pipe, msg)), and each pipe's StreamEngine runs
+ * mechanism.encode on it under its own key and nonce: N seals of one payload.  Here that is one
+ * launch, one lane per subscriber, with a 16-byte record per subscriber instead of a 40-byte
+ * descriptor and a 16-byte segment per frame.  Body i = the MESSAGE body of d_payload[0, len)
+ * with flags byte `flags` (as cz_frame_desc.flags) under subkey d_subs[i].key_idx and nonce
+ * d_subs[i].counter, at d_out + i*out_stride: exactly the bytes cz_seal_batch writes for count
+ * descriptors that share one in_off.
+ * Output ownership as cz_seal_uniform: with an out_stride that is a multiple of 128 (below
+ * 32 MiB), or a multiple of 16 with 64 slots in 16 KiB (out_stride <= 256), the batch owns
+ * count * out_stride bytes and slot bytes past a body are written as zero; with any other
+ * out_stride >= len + 33 the bytes between bodies are left as the caller wrote them.  Full waves
+ * of 16-byte aligned slots store whole lines; partial waves, other strides, and an output base
+ * or payload off 16-byte alignment store lane by lane (correct, not tuned).
+ * count == 0: CZ_OK, nothing launched.  Null pointers, out_stride < len + 33: CZ_EINVAL;
+ * len > CZ_MESSAGE_MAX: CZ_EMSGSIZE (checked before the device is touched).  No device: CZ_EHIP. */
+typedef struct cz_fanout_sub {
+    uint64_t counter;  /* nonce counter of this subscriber's frame */
+    uint32_t key_idx;  /* subkey index */
+    uint32_t reserved; /* 0 */
+} cz_fanout_sub;
+/* Dist.distribute (zmq/socket/pubsub/Dist.java) -> write(pipe, msg) -> mechanism.encode per pipe */
+int cz_seal_fanout(uint32_t count, uint32_t len, const void *d_payload, uint32_t flags,
+                   const cz_fanout_sub *d_subs, const void *d_subkeys,
+                   void *d_out, uint64_t out_stride, void *stream);
+
 /* Synthetic data: fill d_buf with the counter-based SplitMix64 byte stream (seed). */
 int cz_fill(void *d_buf, uint64_t nbytes, uint64_t seed, void *stream);
 /* Measurement: device-to-device copy of nbytes (a multiple of 16) with 16-byte loads and stores,
@@ -352,6 +379,18 @@ void *cz_engine_msg_alloc(cz_engine *e, uint32_t len);
 /* queue one Msg (payload from cz_engine_msg_alloc, or copied into the arena); CZ_ENOMEM when the
  * arena is full (flush first), CZ_EPROTO when the connection has failed */
 int cz_engine_send(cz_engine *e, int conn, const void *payload, uint32_t len, int msg_flags);
+/* PUB fan-out (Dist.distribute, zmq/socket/pubsub/Dist.java): queue ONE Msg for each of the nconn
+ * listed connections, in list order, at this point of the send order.  The payload is staged in
+ * the arena once (or not at all when it already lies there), so N subscribers cost len arena
+ * bytes, not N * len; a multipart message is several calls with CZ_MSG_MORE.  Everything is
+ * checked before anything is queued: an unknown or removed id is CZ_EINVAL, an over-long payload
+ * CZ_EMSGSIZE, a full arena CZ_ENOMEM, each with nothing queued.  Connections that have failed
+ * are skipped (Dist.write drops a pipe it cannot write to); *queued (optional) = frames queued.
+ * An id listed twice gets two frames with consecutive nonces.  flush_out seals a publish's run
+ * of at least cz_tune("fanout_min") frames with one cz_seal_fanout launch; the wire bytes are
+ * those of the same messages queued with cz_engine_send. */
+int cz_engine_publish(cz_engine *e, const int *conns, uint32_t nconn, const void *payload, uint32_t len,
+                      int msg_flags, uint32_t *queued);
 /* seal every queued Msg on the device and V2-frame it into one pinned output in SEND order
  * (valid until the next cz_engine_flush_out).  The flush is pipelined in groups of ~8 MiB+:
  * H2D of a group overlaps the seal + D2H of the one before. */
@@ -580,7 +619,10 @@ int cz_device_ok(void);
  *   "shift16": 1 = segment outputs that are 16-byte but not 128-byte aligned through the
  *              byte-shifted line emitter (default), 0 = 128-byte groups at each output's base
  *   "open_ina" / "seal_ina": 1 = line paths for bodies / payloads off 16-byte alignment with
- *              dword-aligned loads (default), 0 = lane-wise unaligned paths */
+ *              dword-aligned loads (default), 0 = lane-wise unaligned paths
+ *   "fanout_min": cz_engine_flush_out seals a publish's run of at least this many frames with
+ *              cz_seal_fanout (default 2^18: each run is one launch, which must fill the device by itself
+ *              to beat the segment plan's one launch per group); 0 = every publish stays on the segment path */
 int cz_tune(const char *key, int value);
 
 #ifdef __cplusplus

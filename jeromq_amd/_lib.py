@@ -81,6 +81,13 @@ class cz_v2_item(ctypes.Structure):
 assert ctypes.sizeof(cz_v2_frame) == 16 and ctypes.sizeof(cz_v2_item) == 24
 
 
+class cz_fanout_sub(ctypes.Structure):
+    _fields_ = [("counter", ctypes.c_uint64), ("key_idx", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(cz_fanout_sub) == 16
+
+
 class cz_accept_result(ctypes.Structure):
     _fields_ = [("rc", ctypes.c_int32), ("event", ctypes.c_int32), ("slot", ctypes.c_int32),
                 ("reply_len", ctypes.c_uint32)]
@@ -105,6 +112,7 @@ SIGNATURES = {
     "cz_seal_uniform": (_I, [_U32, _U32, _VP, _U64, _VP, _U64, _VP, _U64, _VP, _VP]),
     "cz_seal_uniform_box": (_I, [_U32, _U32, _VP, _U64, _VP, _U64, _VP, _U64, _VP]),
     "cz_open_uniform": (_I, [_U32, _U32, _VP, _U64, _VP, _U64, _VP, _U64, _I, _VP, _VP]),
+    "cz_seal_fanout": (_I, [_U32, _U32, _VP, _U32, _VP, _VP, _VP, _U64, _VP]),
     "cz_plan_order": (_I, [_VP, _U32, _VP]),
     "cz_plan_segments": (_I, [_VP, _U32, _I, _U32, _VP, _U32, ctypes.POINTER(_U32), _VP, _U32,
                               ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
@@ -140,6 +148,7 @@ SIGNATURES = {
     "cz_engine_remove_conn": (_I, [_VP, _I]),
     "cz_engine_msg_alloc": (_VP, [_VP, _U32]),
     "cz_engine_send": (_I, [_VP, _I, _VP, _U32, _I]),
+    "cz_engine_publish": (_I, [_VP, ctypes.POINTER(_I), _U32, _VP, _U32, _I, ctypes.POINTER(_U32)]),
     "cz_engine_flush_out": (_I, [_VP]),
     "cz_engine_wire_out": (_I, [_VP, _I, ctypes.POINTER(_VP), ctypes.POINTER(_U64)]),
     "cz_engine_wire_iov": (_I, [_VP, _I, _VP, _U32, ctypes.POINTER(_U32)]),

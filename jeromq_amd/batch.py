@@ -58,6 +58,31 @@ def seal_uniform(inp, in_stride, out, out_stride, count, length, subkey, counter
                                           counter0, _ptr(flags8), _stream(stream)), "cz_seal_uniform")
 
 
+FANOUT_SUB_DTYPE = np.dtype([("counter", "<u8"), ("key_idx", "<u4"), ("reserved", "<u4")])
+
+
+def seal_fanout(payload, length, flags, subs, subkeys_t, out, out_stride, count, stream=None):
+    """PUB fan-out: seal the ONE `length`-byte payload at payload[0] with MESSAGE flags byte `flags`
+    for `count` subscribers; body i goes to out[i*out_stride] under subkey subs[i].key_idx and nonce
+    subs[i].counter (subs: a device tensor of count 16-byte cz_fanout_sub records, FANOUT_SUB_DTYPE).
+    The bytes are those of seal_batch with `count` descriptors sharing one in_off.  With an
+    out_stride that is a multiple of 128 the batch owns whole slots (zeros past each body)."""
+    _need_cuda_u8(payload, "payload")
+    _need_cuda_u8(out, "out")
+    _need_cuda_u8(subkeys_t, "subkeys")
+    if subs is None or not subs.is_cuda:
+        raise ValueError("subs must be a CUDA (HIP) tensor")
+    if out_stride < length + _lib.CZ_MESSAGE_OVERHEAD:
+        raise ValueError("out_stride smaller than a MESSAGE body")
+    if count:
+        if payload.numel() < length or out.numel() < (count - 1) * out_stride + length + _lib.CZ_MESSAGE_OVERHEAD:
+            raise ValueError("buffer too small for the batch")
+        if subs.numel() * subs.element_size() < count * FANOUT_SUB_DTYPE.itemsize:
+            raise ValueError("subs too small")
+    _lib.check(_lib.lib().cz_seal_fanout(count, length, _ptr(payload), flags, _ptr(subs), _ptr(subkeys_t), _ptr(out),
+                                         out_stride, _stream(stream)), "cz_seal_fanout")
+
+
 def seal_uniform_box(box, box_stride, out, out_stride, count, length, subkey, counter0, stream=None):
     """Uniform seal from the reference's box layout: slot i of `box` holds 0^32 || flags ||
     payload (length = payload bytes), as CurveClientMechanism.encode hands it to Curve.afternm."""

@@ -180,7 +180,33 @@ struct OutMsg {
     uint64_t arena_off;
     uint32_t len;
     uint32_t flags;
+    uint32_t pub = 0;  // cz_engine_publish call this frame belongs to (0: cz_engine_send)
 };
+
+// A run of one publish's frames inside a flush group, sealed by one cz_seal_fanout launch:
+// send-order frames [first, first + count) share payload, length and flags, and their body slots
+// are contiguous at one stride.
+struct FanRun {
+    uint32_t first, count;
+};
+
+// The fan-out runs of pend[fa, fb): maximal runs of consecutive frames of one publish with at
+// least `min_run` frames (0: none).
+void fanout_runs(const std::vector<OutMsg> &pend, uint32_t fa, uint32_t fb, uint32_t min_run, std::vector<FanRun> &runs)
+{
+    runs.clear();
+    if (min_run == 0)
+        return;
+    for (uint32_t i = fa; i < fb;) {
+        uint32_t j = i + 1;
+        if (pend[i].pub)
+            while (j < fb && pend[j].pub == pend[i].pub)
+                j++;
+        if (pend[i].pub && j - i >= min_run)
+            runs.push_back({i, j - i});
+        i = j;
+    }
+}
 
 struct InMsg {
     uint64_t plain_off;
@@ -229,7 +255,8 @@ struct cz_engine {
     HostBuf h_plain;
     std::vector<InMsg> in_msgs;
     // device staging (grows, never shrinks)
-    DevBuf d_in, d_body, d_wire, d_desc, d_seg, d_comb, d_work, d_items, d_status, d_nonces, d_plain;
+    DevBuf d_in, d_body, d_wire, d_desc, d_seg, d_comb, d_work, d_items, d_status, d_nonces, d_plain, d_subs;
+    uint32_t pub_seq = 0;  // id of the last cz_engine_publish call (OutMsg::pub)
     HostBuf h_status, h_nonces;
     HostBuf h_meta;  // pinned staging of descriptors / items / segment lists (async H2D)
     RxPool rxpool;   // every connection's receive buffer
@@ -258,7 +285,7 @@ struct cz_engine {
                 (void)hipStreamDestroy(q);
             }
         for (DevBuf *b : {&subkeys, &d_in, &d_body, &d_wire, &d_desc, &d_seg, &d_comb, &d_work, &d_items, &d_status,
-                          &d_nonces, &d_plain})
+                          &d_nonces, &d_plain, &d_subs})
             b->release();
         for (HostBuf *b : {&arena, &h_wire, &h_plain, &h_status, &h_nonces, &h_meta})
             b->release();
@@ -351,6 +378,19 @@ struct cz_engine {
                     fa = i + 1;
                 }
         }
+        // publishes: inside a group, a run of one publish's frames has contiguous body slots of
+        // one stride (slots follow send order) and leaves the segment plan for one cz_seal_fanout
+        // launch; a publish split by a group edge is two runs.  fan[i]: frame i is in such a run.
+        std::vector<std::vector<FanRun>> fruns(groups.size());
+        std::vector<uint8_t> fan(n, 0);
+        bool any_fan = false;
+        for (size_t gi = 0; gi < groups.size(); gi++) {
+            fanout_runs(pend, groups[gi].fa, groups[gi].fb, fanout_min(), fruns[gi]);
+            for (const FanRun &r : fruns[gi]) {
+                std::fill(fan.begin() + r.first, fan.begin() + r.first + r.count, (uint8_t)1);
+                any_fan = true;
+            }
+        }
         std::vector<uint64_t> soff(groups.size() + 1, 0), coff(groups.size() + 1, 0), woff(groups.size() + 1, 0);
         uint64_t slot = 0, hi = 0;
         for (size_t gi = 0; gi < groups.size(); gi++) {
@@ -361,7 +401,8 @@ struct cz_engine {
                 const OutMsg &m = pend[i];
                 slot += round_up((uint64_t)m.len + CZ_MESSAGE_OVERHEAD, SLOT_ALIGN);
                 hi = std::max<uint64_t>(hi, m.arena_off + m.len);
-                plan_counts(m.len, 0, seg, ns, nc, np);
+                if (!fan[i])
+                    plan_counts(m.len, 0, seg, ns, nc, np);
             }
             g.arena_hi = hi;
             soff[gi + 1] = soff[gi] + ns;
@@ -371,7 +412,8 @@ struct cz_engine {
         const uint64_t nseg = soff[groups.size()], ncomb = coff[groups.size()], npart = woff[groups.size()];
         const uint64_t m_items = 0, m_desc = (uint64_t)n * sizeof(cz_v2_item),
                        m_seg = m_desc + (uint64_t)n * sizeof(cz_frame_desc), m_comb = m_seg + nseg * sizeof(cz_segment),
-                       m_end = m_comb + ncomb * sizeof(cz_combine);
+                       m_subs = m_comb + ncomb * sizeof(cz_combine),
+                       m_end = m_subs + (any_fan ? (uint64_t)n * sizeof(cz_fanout_sub) : 0);
         hipError_t e;
         if ((e = d_in.reserve(std::max<uint64_t>(arena_used, 16))) != hipSuccess ||
             (e = d_body.reserve(slot)) != hipSuccess || (e = d_wire.reserve(wire_total)) != hipSuccess ||
@@ -380,6 +422,7 @@ struct cz_engine {
             (e = d_seg.reserve(std::max<uint64_t>(nseg, 1) * sizeof(cz_segment))) != hipSuccess ||
             (e = d_comb.reserve(std::max<uint64_t>(ncomb, 1) * sizeof(cz_combine))) != hipSuccess ||
             (e = d_work.reserve(std::max<uint64_t>(npart, 1) * 64)) != hipSuccess ||
+            (any_fan && (e = d_subs.reserve((uint64_t)n * sizeof(cz_fanout_sub))) != hipSuccess) ||
             (e = h_wire.reserve(wire_total)) != hipSuccess || (e = h_meta.reserve(m_end)) != hipSuccess)
             return hip_fail(e, "cz_engine: alloc");
         // descriptors and items are built straight into pinned staging (pageable sources would
@@ -387,6 +430,7 @@ struct cz_engine {
         uint8_t *hm = (uint8_t *)h_meta.ptr;
         cz_v2_item *h_items = (cz_v2_item *)(hm + m_items);
         cz_frame_desc *h_desc = (cz_frame_desc *)(hm + m_desc);
+        cz_fanout_sub *h_subs = (cz_fanout_sub *)(hm + m_subs);  // by send index, fan-out frames only
         pt.mark("plan");
         std::vector<hipEvent_t> ev(groups.size(), nullptr), evk(groups.size(), nullptr);
         EvGuard evguard{ev}, evkguard{evk};
@@ -416,15 +460,25 @@ struct cz_engine {
             const Group &g = groups[gi];
             const uint32_t gn = g.fb - g.fa;
             uint64_t bs = g.slot0;
+            // nonces in send order; the group's descriptors (segment-plan frames only) are packed
+            // at the front of its range -- cz_v2_item carries each frame's slot and wire position
+            uint32_t gd = 0;
             for (uint32_t i = g.fa; i < g.fb; i++) {
                 const OutMsg &m = pend[i];
                 Conn &c = conns[m.conn];
                 const uint64_t body = (uint64_t)m.len + CZ_MESSAGE_OVERHEAD;
-                h_desc[i] = {m.arena_off, bs, m.len, c.tx_key, c.nonce++, m.flags & 0xffu, -1};
+                if (fan[i])
+                    h_subs[i] = {c.nonce++, c.tx_key, 0u};
+                else
+                    h_desc[g.fa + gd++] = {m.arena_off, bs, m.len, c.tx_key, c.nonce++, m.flags & 0xffu, -1};
                 h_items[i] = {bs, wpos[i], (uint32_t)body, (uint32_t)CZ_V2_ITEM_HEADER};
                 bs += round_up(body, SLOT_ALIGN);
             }
-            plan_segments(h_desc + g.fa, gn, 0, seg, sg.seg, sg.comb, sg.npart);
+            const std::vector<FanRun> &fr = fruns[gi];
+            // one copy for the group's subscriber records: first run's start to last run's end
+            const uint32_t sub_a = fr.empty() ? 0u : fr.front().first,
+                           sub_b = fr.empty() ? 0u : fr.back().first + fr.back().count;
+            plan_segments(h_desc + g.fa, gd, 0, seg, sg.seg, sg.comb, sg.npart);
             const uint32_t gseg = (uint32_t)sg.seg.size(), gcomb = (uint32_t)sg.comb.size();
             if (gseg != soff[gi + 1] - soff[gi] || gcomb != coff[gi + 1] - coff[gi] || sg.npart != woff[gi + 1] - woff[gi])
                 return fail(CZ_EINVAL, "cz_engine: segment plan disagrees with its count");
@@ -437,8 +491,11 @@ struct cz_engine {
             //     the host builds that group)
             if ((e = hipMemcpyAsync((cz_v2_item *)d_items.ptr + g.fa, h_items + g.fa, (uint64_t)gn * sizeof(cz_v2_item),
                                     hipMemcpyHostToDevice, qh)) != hipSuccess ||
-                (e = hipMemcpyAsync(dd, h_desc + g.fa, (uint64_t)gn * sizeof(cz_frame_desc), hipMemcpyHostToDevice,
-                                    qh)) != hipSuccess ||
+                (gd && (e = hipMemcpyAsync(dd, h_desc + g.fa, (uint64_t)gd * sizeof(cz_frame_desc), hipMemcpyHostToDevice,
+                                           qh)) != hipSuccess) ||
+                (sub_b > sub_a && (e = hipMemcpyAsync((cz_fanout_sub *)d_subs.ptr + sub_a, h_subs + sub_a,
+                                                      (uint64_t)(sub_b - sub_a) * sizeof(cz_fanout_sub),
+                                                      hipMemcpyHostToDevice, qh)) != hipSuccess) ||
                 (gseg && (e = hipMemcpyAsync(dsg, (const cz_segment *)(hm + m_seg) + soff[gi],
                                              (uint64_t)gseg * sizeof(cz_segment), hipMemcpyHostToDevice, qh)) !=
                              hipSuccess) ||
@@ -450,9 +507,19 @@ struct cz_engine {
                 return hip_fail(e, "cz_engine: flush_out H2D");
             // (b) compute stream: seal into body slots, pack behind V2 headers at the send-order
             //     wire positions; (c) D2H stream: the group's wire bytes back
-            if ((qh != qk && (e = hipStreamWaitEvent(qk, ev[gi], 0)) != hipSuccess) ||
-                (e = czk_seal_segments(dd, dsg, gseg, dcb, gcomb, d_in.ptr, d_body.ptr, subkeys.ptr,
-                                       (uint8_t *)d_work.ptr + 64 * woff[gi], qk)) != hipSuccess ||
+            if (qh != qk && (e = hipStreamWaitEvent(qk, ev[gi], 0)) != hipSuccess)
+                return hip_fail(e, "cz_engine: flush_out");
+            for (const FanRun &r : fr) {
+                const OutMsg &m = pend[r.first];
+                if ((e = czk_seal_fanout((const uint8_t *)d_in.ptr + m.arena_off, m.len, m.flags & 0xffu,
+                                         (const cz_fanout_sub *)d_subs.ptr + r.first, subkeys.ptr,
+                                         (uint8_t *)d_body.ptr + h_items[r.first].src_off,
+                                         round_up((uint64_t)m.len + CZ_MESSAGE_OVERHEAD, SLOT_ALIGN), r.count, qk)) !=
+                    hipSuccess)
+                    return hip_fail(e, "cz_engine: flush_out fan-out");
+            }
+            if ((gseg && (e = czk_seal_segments(dd, dsg, gseg, dcb, gcomb, d_in.ptr, d_body.ptr, subkeys.ptr,
+                                                (uint8_t *)d_work.ptr + 64 * woff[gi], qk)) != hipSuccess) ||
                 (e = czk_v2_copy((const cz_v2_item *)d_items.ptr + g.fa, gn, d_body.ptr, d_wire.ptr, qk)) !=
                     hipSuccess ||
                 (qo != qk && ((e = hipEventRecord(evk[gi], qk)) != hipSuccess ||
@@ -992,6 +1059,54 @@ int cz_engine_send(cz_engine *e, int conn, const void *payload, uint32_t len, in
     if (msg_flags & CZ_MSG_COMMAND)
         fl |= 0x02;
     e->pend.push_back({(uint32_t)conn, off, len, fl});
+    return CZ_OK;
+}
+
+int cz_engine_publish(cz_engine *e, const int *conns, uint32_t nconn, const void *payload, uint32_t len,
+                      int msg_flags, uint32_t *queued)
+{
+    if (queued)
+        *queued = 0;
+    if (!e || (nconn && !conns) || (len && !payload))
+        return fail(CZ_EINVAL, "cz_engine_publish: null pointer");
+    // everything is checked before anything is queued
+    uint32_t live = 0;
+    for (uint32_t k = 0; k < nconn; k++) {
+        const Conn *c = e->conn(conns[k]);
+        if (!c)
+            return CZ_EINVAL;
+        live += c->error ? 0u : 1u;  // a failed connection is skipped, as Dist.write drops its pipe
+    }
+    if (len > (uint32_t)CZ_MESSAGE_MAX)
+        return fail(CZ_EMSGSIZE, "cz_engine_publish: %u-byte payload exceeds CZ_MESSAGE_MAX", len);
+    if (live == 0)
+        return CZ_OK;
+    const uint8_t *base = (const uint8_t *)e->arena.ptr;
+    const uint8_t *p = (const uint8_t *)payload;
+    uint64_t off;
+    if (len && p >= base && p + len <= base + e->arena_used) {
+        off = (uint64_t)(p - base);  // allocated by cz_engine_msg_alloc: no copy
+    } else {
+        uint8_t *dst = (uint8_t *)cz_engine_msg_alloc(e, len);  // staged once for every subscriber
+        if (!dst)
+            return fail(CZ_ENOMEM, "cz_engine_publish: arena full (%llu bytes), flush first",
+                        (unsigned long long)e->arena_cap);
+        if (len)
+            memcpy(dst, p, len);
+        off = (uint64_t)(dst - base);
+    }
+    uint32_t fl = 0;
+    if (msg_flags & CZ_MSG_MORE)
+        fl |= 0x01;
+    if (msg_flags & CZ_MSG_COMMAND)
+        fl |= 0x02;
+    if (++e->pub_seq == 0)
+        e->pub_seq = 1;
+    for (uint32_t k = 0; k < nconn; k++)
+        if (!e->conns[(size_t)conns[k]].error)
+            e->pend.push_back({(uint32_t)conns[k], off, len, fl, e->pub_seq});
+    if (queued)
+        *queued = live;
     return CZ_OK;
 }
 

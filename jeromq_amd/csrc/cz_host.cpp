@@ -23,6 +23,8 @@ hipError_t czk_seal_uniform_box(const void *, uint64_t, void *, uint64_t, uint32
                                 hipStream_t);
 hipError_t czk_seal_uniform(const void *, uint64_t, void *, uint64_t, uint32_t, uint32_t, const void *, uint64_t,
                             const uint8_t *, hipStream_t);
+hipError_t czk_seal_fanout(const void *, uint32_t, uint32_t, const cz_fanout_sub *, const void *, void *, uint64_t,
+                           uint32_t, hipStream_t);
 hipError_t czk_seal_desc(const cz_frame_desc *, const uint32_t *, uint32_t, const void *, void *, const void *,
                          hipStream_t);
 hipError_t czk_open_desc(const cz_frame_desc *, const uint32_t *, uint32_t, const void *, void *, const void *,
@@ -251,6 +253,17 @@ uint64_t nacl_one_bytes()
 {
     return std::max<uint64_t>(g_nacl_one_bytes.load(std::memory_order_relaxed), czk_nacl_one_max());
 }
+
+// cz_engine_flush_out: a publish's run of at least this many frames leaves the segment plan for one
+// cz_seal_fanout launch; 0 = never (cz_tune "fanout_min").  Each run is a launch of its own on the
+// group's stream, so a run pays off only when it fills the device by itself: a launch of up to
+// 16 384 x 4 KiB lanes takes the 0.13 ms one lane needs for its 65 blocks, and 256 publishes to
+// 1024 connections flushed 2.3x slower routed than in the segment plan, whose one launch per group
+// holds every frame ("PUB fan-out").  2^18 is the smallest measured count at
+// which the run's own launch is throughput-bound and ahead of the segment kernels.
+static std::atomic<uint32_t> g_fanout_min{1u << 18};
+
+uint32_t fanout_min() { return g_fanout_min.load(std::memory_order_relaxed); }
 
 // NaCl box/open of one message on the device.  A MESSAGE is the NaCl box of
 // 0^32 || flags || payload, so m[32] rides as the flags byte and m[33:] as the payload; for open
@@ -489,6 +502,11 @@ int cz_tune(const char *key, int value)
                                std::memory_order_relaxed);
         return old;
     }
+    if (key && strcmp(key, "fanout_min") == 0) {
+        const int old = (int)g_fanout_min.load(std::memory_order_relaxed);
+        g_fanout_min.store((uint32_t)std::max(value, 0), std::memory_order_relaxed);
+        return old;
+    }
     int old = czk_tune(key, value);
     if (old < 0)
         return fail(CZ_EINVAL, "cz_tune: unknown key");
@@ -608,6 +626,24 @@ int cz_seal_uniform(uint32_t count, uint32_t len, const void *d_in, uint64_t in_
     hipError_t e = czk_seal_uniform(d_in, in_stride, d_out, out_stride, count, len, d_subkey, counter0, d_flags8,
                                     (hipStream_t)stream);
     return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_seal_uniform");
+}
+
+int cz_seal_fanout(uint32_t count, uint32_t len, const void *d_payload, uint32_t flags, const cz_fanout_sub *d_subs,
+                   const void *d_subkeys, void *d_out, uint64_t out_stride, void *stream)
+{
+    if (count == 0)
+        return CZ_OK;
+    if ((len && !d_payload) || !d_subs || !d_subkeys || !d_out)
+        return fail(CZ_EINVAL, "cz_seal_fanout: null pointer");
+    if (len > (uint32_t)CZ_MESSAGE_MAX)
+        return fail(CZ_EMSGSIZE, "cz_seal_fanout: %u-byte payload exceeds CZ_MESSAGE_MAX", len);
+    if (out_stride < (uint64_t)len + CZ_MESSAGE_OVERHEAD)
+        return fail(CZ_EINVAL, "cz_seal_fanout: out_stride smaller than the body");
+    if (!uniform_span(count, out_stride, (uint64_t)len + CZ_MESSAGE_OVERHEAD, nullptr))
+        return fail(CZ_EINVAL, "cz_seal_fanout: count x out_stride overflows the address space");
+    hipError_t e = czk_seal_fanout(d_payload, len, flags, d_subs, d_subkeys, d_out, out_stride, count,
+                                   (hipStream_t)stream);
+    return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_seal_fanout");
 }
 
 int cz_seal_uniform_box(uint32_t count, uint32_t len, const void *d_box, uint64_t box_stride, void *d_out,

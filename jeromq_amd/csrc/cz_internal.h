@@ -17,6 +17,8 @@ hipError_t czk_seal_desc(const cz_frame_desc *, const uint32_t *, uint32_t, cons
                          hipStream_t);
 hipError_t czk_open_desc(const cz_frame_desc *, const uint32_t *, uint32_t, const void *, void *, const void *,
                          uint16_t *, uint64_t *, hipStream_t);
+hipError_t czk_seal_fanout(const void *, uint32_t, uint32_t, const cz_fanout_sub *, const void *, void *, uint64_t,
+                           uint32_t, hipStream_t);
 hipError_t czk_subkeys(const void *, void *, uint32_t, const uint8_t *, hipStream_t);
 hipError_t czk_seal_segments(const cz_frame_desc *, const cz_segment *, uint32_t, const cz_combine *, uint32_t,
                              const void *, void *, const void *, void *, hipStream_t);
@@ -33,6 +35,7 @@ namespace czi {
 int fail(int code, const char *fmt, ...);
 int hs_thread_init();  // the calling thread's handshake context (cz_handshake.cpp)
 uint64_t nacl_one_bytes();  // boxes up to this size take k_nacl_one (cz_tune "nacl_one_max")
+uint32_t fanout_min();      // publish runs of at least this many frames take k_seal_fanout (cz_tune "fanout_min")
 int hip_fail(hipError_t e, const char *where);
 const uint8_t *prefix_for(int direction);
 void plan_segments(const cz_frame_desc *h_desc, uint32_t count, int open, uint32_t seg_blocks,

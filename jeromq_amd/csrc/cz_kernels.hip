@@ -2662,6 +2662,92 @@ __global__ __launch_bounds__(BLOCK) CZ_OCC CZ_OPEN_UNI_OCC void k_seal_uniform_i
                                                allow_un0);
 }
 
+// PUB fan-out (Dist.distribute -> write(pipe, msg) -> mechanism.encode per pipe): one lane per
+// subscriber, every lane sealing the SAME len-byte payload and flags byte under its own subkey
+// (subkeys + 32 * subs[i].key_idx) and nonce counter (subs[i].counter) into slot out + i*out_stride
+// -- the bytes k_seal_desc writes for `count` descriptors sharing one in_off.  Key and high nonce
+// word are per lane, so the Salsa rounds are the non-UN0 ones; the payload pointer is a kernel
+// argument, wave-uniform by construction.
+// Staging as seal_uniform_body: a full wave of 16-byte aligned slots takes EmitLines (ST_LINES:
+// out_stride % 128 == 0) or EmitRegion (ST_REGION: 64 slots <= 16 KiB); partial waves, other
+// strides, and an output base or payload off 16-byte alignment store lane-wise and byte-exact
+// (EmitDirect) -- correct at every layout, not tuned in this version.  `owns`: the batch owns its
+// whole slots (czk_seal_fanout), so the direct path zeroes the slot bytes past the body too.
+// A copy of p that the compiler cannot prove wave-uniform (an empty asm on a VGPR: no instruction,
+// the value is unchanged), so loads through it stay per-lane vector loads.  The payload off 16-byte
+// alignment needs it: the backend turns a wave-uniform 16-byte load into an s_load_dwordx4 even at
+// alignment 1, and the scalar unit drops the low two address bits (payload at byte phase 1 read
+// from phase 0; found by tests/test_gpu_fanout.py::test_layouts).
+__device__ __forceinline__ const uint8_t *per_lane_ptr(const uint8_t *p)
+{
+    asm volatile("" : "+v"(p));
+    return p;
+}
+#ifdef CZ_FANOUT_VGPR_PAYLOAD
+// A/B leg: every path reads the payload per lane (window loads and funnel in VGPRs, as in a
+// multi-key uniform seal)
+#define CZ_FANOUT_SRC(p) per_lane_ptr(p)
+#else
+#define CZ_FANOUT_SRC(p) (p)
+#endif
+template <int ST, bool PAIR>
+__global__ __launch_bounds__(BLOCK) CZ_OCC CZ_OPEN_UNI_OCC void k_seal_fanout(
+    const uint8_t *__restrict__ payload, uint32_t len, uint32_t flags, const cz_fanout_sub *__restrict__ subs,
+    const uint8_t *__restrict__ subkeys, uint8_t *__restrict__ out, uint64_t out_stride, uint32_t count, int owns)
+{
+    extern __shared__ uint4 smem[];
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    const uint32_t wave_first = i & ~63u;
+    if (wave_first >= count)
+        return;
+    const bool full_wave = wave_first + 64u <= count;
+    const u32 mlen = len + 33u;
+    const u32 fl = flags & 0xffu;
+    const uint8_t *src = CZ_FANOUT_SRC(payload);
+    if (ST != ST_DIRECT && full_wave) {
+        const cz_fanout_sub sb = subs[i];
+        u32 key[8];
+        load_key(subkeys + 32ull * sb.key_idx, key);
+        uint8_t *dst = out + (uint64_t)i * out_stride;
+        const u32 lane = threadIdx.x & 63u;
+        if constexpr (ST == ST_LINES) {
+            using EmL = EmitLinesSeal;
+            EmL em{smem + (threadIdx.x >> 6) * (LINE_LDS_BYTES / 16), out + (uint64_t)wave_first * out_stride,
+                   dst, out_stride, lane, mlen, 0u, true,
+                   smem + (WAVES * LINE_LDS_BYTES + (threadIdx.x >> 6) * HOLD_LDS_BYTES) / 16};
+            seal_frame<MODE_ZMQ, true, EmL, PAIR, false, true, 16>(src, len, fl, sb.counter, key, em);
+            // EmitLines ends at the body's last line; a slot with more lines than that is owned too
+            const u32 body_lines = (mlen + 127u) & ~127u;
+            if (out_stride > body_lines)
+                zero_bytes(dst + body_lines, (u32)(out_stride - body_lines));
+        } else {
+            const u32 st = (u32)out_stride;
+            EmitRegionSeal em{smem + (threadIdx.x >> 6) * ((64u * st) >> 4), out + (uint64_t)wave_first * out_stride, st,
+                              lane, mlen};
+            seal_frame<MODE_ZMQ, true, EmitRegionSeal, PAIR, false, true, 16>(src, len, fl, sb.counter, key, em);
+        }
+        return;
+    }
+    if (i >= count)
+        return;
+    const cz_fanout_sub sb = subs[i];
+    u32 key[8];
+    load_key(subkeys + 32ull * sb.key_idx, key);
+    uint8_t *dst = out + (uint64_t)i * out_stride;
+    if (aligned16(src, dst)) {
+        EmitDirect<true> em{dst, mlen};
+        seal_frame<MODE_ZMQ, true, EmitDirect<true>, PAIR>(src, len, fl, sb.counter, key, em);
+    } else if ((((uintptr_t)src) & 15u) == 0) {
+        EmitDirect<false> em{dst, mlen};
+        seal_frame<MODE_ZMQ, true, EmitDirect<false>, PAIR>(src, len, fl, sb.counter, key, em);
+    } else {
+        EmitDirect<false> em{dst, mlen};
+        seal_frame<MODE_ZMQ, false>(per_lane_ptr(src), len, fl, sb.counter, key, em);
+    }
+    if (owns && out_stride > mlen)
+        zero_bytes(dst + mlen, (u32)(out_stride - mlen));
+}
+
 #if CZ_KPART_HAS(3)
 __global__ __launch_bounds__(BLOCK) void k_seal_desc(const cz_frame_desc *__restrict__ desc,
                                                       const uint32_t *__restrict__ order, uint32_t count,
@@ -3726,6 +3812,35 @@ hipError_t czk_seal_uniform_box(const void *in, uint64_t in_stride, void *out, u
         hipLaunchKernelGGL((k_seal_uniform<ST_DIRECT, true, MODE_BOX>), grid, dim3(BLOCK), 0, s, (const uint8_t *)in,
                            in_stride, (uint8_t *)out, out_stride, count, len, (const uint8_t *)subkey, counter0, nullptr,
                            g_un0);
+    return hipGetLastError();
+}
+
+// PUB fan-out: `count` seals of one payload (k_seal_fanout).  The batch owns whole slots when
+// out_stride is a multiple of 128 (below 32 MiB: EmitLines' buffer-store offsets, up to
+// 64 * stride, stay below 2^31) or a multiple of 16 with 64 slots in REGION_MAX bytes, whatever the
+// base alignments: the staged emitters write the zeros past a body with its lines, the lane-wise
+// path (partial waves, a base or payload off 16-byte alignment) writes them itself.
+hipError_t czk_seal_fanout(const void *payload, uint32_t len, uint32_t flags, const cz_fanout_sub *subs,
+                           const void *subkeys, void *out, uint64_t out_stride, uint32_t count, hipStream_t s)
+{
+    if (count == 0)
+        return hipSuccess;
+    dim3 grid((count + BLOCK - 1) / BLOCK);
+    const bool owns = (out_stride % 128 == 0 && out_stride < (1ull << 25)) ||
+                      (out_stride % 16 == 0 && 64 * out_stride <= REGION_MAX);
+    const bool al = ((((uintptr_t)payload | (uintptr_t)out | out_stride) & 15u) == 0);
+    const int st = count >= 64u ? pick_staging(out_stride, len + 33u, al) : ST_DIRECT;
+#define CZ_FANOUT_LAUNCH(ST, PR, LDS)                                                                          \
+    hipLaunchKernelGGL((k_seal_fanout<ST, PR>), grid, dim3(BLOCK), (LDS), s, (const uint8_t *)payload, len, flags, \
+                       subs, (const uint8_t *)subkeys, (uint8_t *)out, out_stride, count, owns ? 1 : 0)
+    // whole-line input loads as czk_seal_uniform: not for the small frames of the region stager
+    if (st == ST_LINES)
+        CZ_FANOUT_LAUNCH(ST_LINES, true, WAVES * (LINE_LDS_BYTES + HOLD_LDS_BYTES));
+    else if (st == ST_REGION)
+        CZ_FANOUT_LAUNCH(ST_REGION, false, (unsigned)(WAVES * 64 * out_stride));
+    else
+        CZ_FANOUT_LAUNCH(ST_DIRECT, true, 0);
+#undef CZ_FANOUT_LAUNCH
     return hipGetLastError();
 }
 

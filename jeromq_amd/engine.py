@@ -5,6 +5,7 @@ device batch per flush and socket-ready ZMTP v2 wire streams per connection.
     eng = CurveBatchEngine(arena_bytes=1 << 26)
     c = eng.add_connection(precom, as_server=False)          # CurveClientMechanism state
     eng.send(c, b"payload", more=False)
+    eng.publish([c, c2, c3], b"payload")                      # one payload to many (PUB fan-out)
     eng.flush_out(); wire = eng.wire_out(c)                   # bytes for the socket
     eng.recv(c, received_bytes); eng.flush_in()
     for payload, flags in eng.messages_in(c): ...
@@ -90,6 +91,24 @@ class CurveBatchEngine:
             buf = ctypes.create_string_buffer(b, len(b)) if b else None
             ptr, n = (ctypes.addressof(buf) if buf else None), len(b)
         return self._L.cz_engine_send(self._h, conn, ptr, n, flags)
+
+    def publish(self, conns, payload, more=False, command=False):
+        """PUB fan-out (Dist.distribute): queue the one payload for every connection in `conns`, in
+        list order; it is staged in the arena once.  Connections that have failed are skipped.
+        Returns the number of frames queued; an unknown id, an over-long payload or a full arena
+        raises with nothing queued."""
+        flags = (_lib.CZ_MSG_MORE if more else 0) | (_lib.CZ_MSG_COMMAND if command else 0)
+        if isinstance(payload, ctypes.Array):
+            ptr, n = ctypes.addressof(payload), ctypes.sizeof(payload)
+        else:
+            b = bytes(payload)
+            buf = ctypes.create_string_buffer(b, len(b)) if b else None
+            ptr, n = (ctypes.addressof(buf) if buf else None), len(b)
+        ids = (ctypes.c_int * max(len(conns), 1))(*conns)
+        queued = ctypes.c_uint32()
+        _lib.check(self._L.cz_engine_publish(self._h, ids, len(conns), ptr, n, flags, ctypes.byref(queued)),
+                   "cz_engine_publish")
+        return queued.value
 
     def flush_out(self):
         _lib.check(self._L.cz_engine_flush_out(self._h), "cz_engine_flush_out")

@@ -1,0 +1,283 @@
+#!/usr/bin/env python3
+"""PUB fan-out: one payload sealed for N subscribers, each under its own key and nonce.
+
+Device legs (HIP-event time of back-to-back launches on device-resident buffers, one warm-up round,
+median of --reps rounds, the legs interleaved inside every round), for N in {64, 1024, 16384, 2^18}
+x len in {100, 4096}, plus len 65536 at N <= 16384; body slots of round_up(len + 33, 128) bytes,
+one distinct key per subscriber:
+  (a) cz_seal_fanout;
+  (b) what the library offered before it: N descriptors sharing one in_off through
+      cz_plan_segments + cz_seal_segments.  The host planning (descriptors + plan) and the metadata
+      H2D are timed apart from the kernels (time.perf_counter around work that ends in a synchronise);
+  (b') the same descriptors planned as cz_engine_flush_out would plan a flush that holds only this
+      publish: segment length from the batch size (short segments for a small batch, so that a few
+      frames spread over many lanes), kernels only;
+  (c) cz_seal_uniform under ONE key at the same count and len (N payload slots): the yardstick a
+      multi-key kernel cannot beat by much;
+  (a') with --ab-lib: cz_seal_fanout of a second build of the library (tools/build_variant.sh),
+      loaded into the same process and timed in the same rounds.
+
+Engine leg: publish + flush_out of --engine-len bytes to --engine-conns connections x
+--engine-msgs messages against the same traffic through per-connection send copies (the `engine`
+config's shape: N x the arena bytes and H2D), wall clock, legs interleaved; the publish leg runs with
+the fan-out routing forced on (cz_tune "fanout_min" = 64) and forced off (2^30); a pinned D2H copy of the
+same wire bytes is timed beside them as the floor a flush cannot go below.
+
+Writes one JSON (default profiles/fanout/fanout.json) and prints it."""
+import argparse
+import ctypes
+import json
+import math
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SIZES = (64, 1024, 16384, 1 << 18)
+LENS = (100, 4096, 65536)
+LONG_MAX_N = 16384
+
+
+def round_up(v, a):
+    return (v + a - 1) // a * a
+
+
+def engine_seg_blocks(total, longest):
+    """the segment length cz_engine_flush_out picks (batch_seg_blocks, cz_internal.h)"""
+    s1 = 2
+    while (s1 + 1) * (s1 + 1) * 18 <= longest:
+        s1 += 1
+    return min(128, max((total + 65535) // 65536, s1))
+
+
+def event_ms(torch, fn, inner):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(inner):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / inner
+
+
+def device_rows(args, torch, dev, batch, _lib, ab):
+    L = _lib.lib()
+    rows = []
+    for length in args.lens:
+        for n in args.sizes:
+            if length > 4096 and n > LONG_MAX_N:
+                continue
+            stride = round_up(length + 33, 128)
+            in_stride = round_up(length, 16)
+            payload = torch.empty(round_up(length, 16) + 256, dtype=torch.uint8, device=dev)
+            batch.fill(payload, 1)
+            uni_in = torch.empty(n * in_stride + 256, dtype=torch.uint8, device=dev)
+            batch.fill(uni_in, 2)
+            sub = torch.empty(n * 32, dtype=torch.uint8, device=dev)
+            batch.fill(sub, 3)
+            sub = sub.view(n, 32)
+            out = torch.empty(n * stride, dtype=torch.uint8, device=dev)
+            rng = np.random.default_rng(n + length)
+            subs = np.zeros(n, dtype=batch.FANOUT_SUB_DTYPE)
+            subs["counter"] = rng.integers(0, 1 << 63, size=n, dtype=np.uint64)
+            subs["key_idx"] = np.arange(n)
+            d_subs = torch.from_numpy(subs.view(np.uint8).copy()).to(dev)
+
+            # (b) host planning and metadata H2D, timed apart
+            def plan():
+                desc = np.zeros(n, dtype=batch.DESC_DTYPE)
+                desc["out_off"] = np.arange(n, dtype=np.uint64) * np.uint64(stride)
+                desc["len"] = length
+                desc["key_idx"] = subs["key_idx"]
+                desc["counter"] = subs["counter"]
+                desc["prev"] = -1
+                return desc, batch.SegmentPlan(desc, seg_blocks=args.seg_blocks or batch.SEG_BLOCKS)
+
+            nblk = (length + 33 + 63) // 64
+            short = engine_seg_blocks(n * nblk, nblk)
+
+            def upload(desc, pl):
+                d = torch.from_numpy(desc.view(np.uint8)).to(dev)
+                pl.to(dev)
+                torch.cuda.synchronize()
+                return d
+
+            t_plan, t_h2d = [], []
+            for rep in range(args.reps + 1):
+                t0 = time.perf_counter()
+                desc, pl = plan()
+                t1 = time.perf_counter()
+                d_desc = upload(desc, pl)
+                t2 = time.perf_counter()
+                if rep:
+                    t_plan.append(t1 - t0)
+                    t_h2d.append(t2 - t1)
+            pl_short = batch.SegmentPlan(desc, seg_blocks=short).to(dev)
+
+            legs = {
+                "fanout": lambda: batch.seal_fanout(payload, length, 0, d_subs, sub, out, stride, n),
+                "segments": lambda: batch.seal_segments(d_desc, pl, payload, out, sub),
+                "segments_short": lambda: batch.seal_segments(d_desc, pl_short, payload, out, sub),
+                "uniform": lambda: batch.seal_uniform(uni_in, in_stride, out, stride, n, length, sub[0], 7),
+            }
+            if ab is not None:
+                stream = torch.cuda.current_stream().cuda_stream
+                legs["fanout_ab"] = lambda: _lib.check(ab.cz_seal_fanout(
+                    n, length, payload.data_ptr(), 0, d_subs.data_ptr(), sub.data_ptr(), out.data_ptr(), stride, stream))
+            # sanity at the timed shape: the legs that seal the same frames agree
+            legs["fanout"]()
+            got = out.clone()
+            legs["segments"]()
+            torch.cuda.synchronize()
+            assert torch.equal(got.view(n, stride)[:, :length + 33], out.view(n, stride)[:, :length + 33]), \
+                "cz_seal_fanout and cz_seal_segments disagree"
+            del got
+            inner = {}
+            for k, fn in legs.items():     # warm-up, and enough launches for a ~2 ms window
+                inner[k] = max(1, min(200, math.ceil(2.0 / max(event_ms(torch, fn, 1), 1e-3))))
+            times = {k: [] for k in legs}
+            for rep in range(args.reps):
+                for k, fn in legs.items():
+                    times[k].append(event_ms(torch, fn, inner[k]))
+            body_bytes = n * (length + 33)
+            row = {"n": n, "len": length, "out_stride": stride, "segments": pl.nseg, "combines": pl.ncomb,
+                   "short_seg_blocks": short, "short_segments": pl_short.nseg,
+                   "plan_host_ms": round(statistics.median(t_plan) * 1e3, 4),
+                   "plan_h2d_ms": round(statistics.median(t_h2d) * 1e3, 4),
+                   "plan_metadata_bytes": int(desc.nbytes + pl.segments.nbytes + pl.combines.nbytes),
+                   "fanout_metadata_bytes": int(subs.nbytes)}
+            for k in legs:
+                med = statistics.median(times[k])
+                row[k + "_ms"] = round(med, 5)
+                row[k + "_all_ms"] = [round(t, 5) for t in times[k]]
+                row[k + "_gib_s"] = round(body_bytes / (med * 1e-3) / 2**30, 2)
+                row[k + "_launches_per_window"] = inner[k]
+            rows.append(row)
+            print(f"n={n} len={length}: " + ", ".join(f"{k} {row[k + '_ms']} ms" for k in legs), file=sys.stderr)
+            del payload, uni_in, sub, out, d_subs, d_desc, pl, pl_short
+            torch.cuda.empty_cache()
+    return rows
+
+
+def engine_leg(args, torch, _lib):
+    from jeromq_amd.engine import CurveBatchEngine
+    L = _lib.lib()
+    nc, nm, length = args.engine_conns, args.engine_msgs, args.engine_len
+    body = length + 33
+    wire_bytes = nc * nm * (body + (9 if body > 255 else 2))
+    payloads = [np.random.default_rng(m).integers(0, 256, size=length, dtype=np.uint8).tobytes() for m in range(nm)]
+
+    def make(arena):
+        e = CurveBatchEngine(arena_bytes=arena)
+        cc = [e.add_connection(np.random.default_rng(1000 + i).integers(0, 256, size=32, dtype=np.uint8).tobytes())
+              for i in range(nc)]
+        return e, cc
+
+    pub, pc = make(nm * round_up(length, 16) + 4096)
+    snd, sc = make(nc * nm * round_up(length, 16) + 4096)
+    ids = (ctypes.c_int * nc)(*pc)
+
+    def run_publish(fanout_min):
+        old = L.cz_tune(b"fanout_min", fanout_min)
+        try:
+            t0 = time.perf_counter()
+            for p in payloads:
+                _lib.check(L.cz_engine_publish(pub._h, ids, nc, p, length, 0, None), "cz_engine_publish")
+            t1 = time.perf_counter()
+            pub.flush_out()
+            return t1 - t0, time.perf_counter() - t1
+        finally:
+            L.cz_tune(b"fanout_min", old)
+
+    def run_send():
+        t0 = time.perf_counter()
+        send, h = L.cz_engine_send, snd._h
+        for p in payloads:
+            for c in sc:
+                if send(h, c, p, length, 0):
+                    raise RuntimeError("cz_engine_send failed: " + _lib.last_error())
+        t1 = time.perf_counter()
+        snd.flush_out()
+        return t1 - t0, time.perf_counter() - t1
+
+    d_wire = torch.empty(wire_bytes, dtype=torch.uint8, device="cuda:0")
+    h_wire = torch.empty(wire_bytes, dtype=torch.uint8).pin_memory()
+
+    def run_d2h():
+        t0 = time.perf_counter()
+        h_wire.copy_(d_wire, non_blocking=True)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    res = {"publish_queue": [], "publish_fanout_flush": [], "publish_segments_flush": [], "send_queue": [],
+           "send_flush": [], "d2h": []}
+    for rep in range(args.reps + 1):
+        pq, pf = run_publish(64)
+        _, ps = run_publish(1 << 30)
+        sq, sf = run_send()
+        d = run_d2h()
+        if rep == 0:
+            continue
+        for k, v in zip(res, (pq, pf, ps, sq, sf, d)):
+            res[k].append(v)
+    out = {"connections": nc, "messages": nm, "len": length, "wire_bytes": wire_bytes,
+           "fanout_min_default": L.cz_tune(b"fanout_min", 64), "clock": "time.perf_counter",
+           "publish_arena_bytes": nm * round_up(length, 16), "send_arena_bytes": nc * nm * round_up(length, 16)}
+    L.cz_tune(b"fanout_min", out["fanout_min_default"])
+    for k, v in res.items():
+        out[k + "_ms"] = round(statistics.median(v) * 1e3, 3)
+        out[k + "_all_ms"] = [round(t * 1e3, 3) for t in v]
+    for k in ("publish_fanout_flush", "publish_segments_flush", "send_flush", "d2h"):
+        out[k + "_gib_s"] = round(wire_bytes / statistics.median(res[k]) / 2**30, 2)
+    pub.close()
+    snd.close()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--sizes", type=int, nargs="*", default=list(SIZES))
+    ap.add_argument("--lens", type=int, nargs="*", default=list(LENS))
+    ap.add_argument("--seg-blocks", type=int, default=0, help="segment length of leg (b) (default: the library's)")
+    ap.add_argument("--ab-lib", default=None, help="a second build of the library: its cz_seal_fanout as leg (a')")
+    ap.add_argument("--ab-name", default=None, help="what the second build is (recorded in the JSON)")
+    ap.add_argument("--engine-conns", type=int, default=1024)
+    ap.add_argument("--engine-msgs", type=int, default=256)
+    ap.add_argument("--engine-len", type=int, default=4096)
+    ap.add_argument("--no-engine", action="store_true")
+    ap.add_argument("--no-device", action="store_true", help="skip the device legs")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fanout", "fanout.json"))
+    args = ap.parse_args()
+    if args.reps < 5:
+        ap.error("--reps must be at least 5")
+    import torch
+    from jeromq_amd import _lib, batch, build
+    assert torch.cuda.is_available(), "fanout_bench needs a GPU"
+    dev = torch.device("cuda:0")
+    ab = None
+    if args.ab_lib:
+        ab = ctypes.CDLL(os.path.abspath(args.ab_lib))
+        ab.cz_seal_fanout.restype, ab.cz_seal_fanout.argtypes = _lib.SIGNATURES["cz_seal_fanout"]
+    kernels = ["k_seal_fanout<1, true>", "k_seal_fanout<2, false>", "k_seal_fanout<0, true>"]
+    out = {"device": torch.cuda.get_device_name(0), "library": _lib.lib().cz_version().decode(),
+           "fanout_kernels_sha256": build.kernel_code_sha256(_lib.LIB_PATH, kernels), "reps": args.reps,
+           "clock_device": "hipEvent (torch.cuda.Event), median", "ab_lib": args.ab_name or args.ab_lib}
+    if not args.no_device:
+        out["device_legs"] = device_rows(args, torch, dev, batch, _lib, ab)
+    if not args.no_engine:
+        out["engine"] = engine_leg(args, torch, _lib)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
