@@ -239,6 +239,65 @@ int cz_seal_fanout(uint32_t count, uint32_t len, const void *d_payload, uint32_t
                    const cz_fanout_sub *d_subs, const void *d_subkeys,
                    void *d_out, uint64_t out_stride, void *stream);
 
+/* ---- 3d. grouped fan-out: many publishes sealed in one call -------------------------
+ * A publisher under load hands Dist.distribute one Msg after another, each to its own list of
+ * pipes; one cz_seal_fanout launch per Msg runs them one after the other, each far too small for
+ * the device.  Here R runs -- each the cz_seal_fanout of one payload for `count` subscribers -- are
+ * one call of at most three launches whatever R: one lane per (run, subscriber), every run padded
+ * to whole 64-lane waves, a per-wave record naming the run a wave serves.  Planner and launch as
+ * cz_plan_segments + cz_seal_segments.
+ * Run r seals d_in[payload_off, payload_off + len) with flags byte `flags` for subscribers
+ * d_subs[first_sub .. first_sub + count), body j at d_out + out_off + j*out_stride: byte for byte
+ * what cz_seal_fanout(count, len, d_in + payload_off, flags, d_subs + first_sub, d_subkeys,
+ * d_out + out_off, out_stride) writes, ownership rule of section 3c per run included.
+ * CALLER'S CONTRACT: the output ranges of different runs (count * out_stride bytes for a run that
+ * owns its slots, (count - 1) * out_stride + len + 33 otherwise) must not overlap; runs may share
+ * payloads and subscriber records.
+ * The staging class of a wave (line emitter, region emitter, lane-wise) is the one cz_seal_fanout
+ * picks for its run alone, from the run's stride and length and the 16-byte alignment of
+ * d_in + payload_off and d_out + out_off; partial waves are lane-wise.  The planner sorts waves by
+ * class, longest payload first inside a class.  The class only decides which launch a wave rides
+ * in: the kernel re-checks the run's alignment and strides itself and stores lane-wise when they
+ * do not fit, so a table planned for other base addresses is slower, never wrong. */
+typedef struct cz_fanout_run {
+    uint64_t payload_off; /* payload's byte offset in d_in */
+    uint64_t out_off;     /* first body slot's byte offset in d_out */
+    uint64_t out_stride;  /* >= len + 33 */
+    uint32_t len;         /* payload bytes, <= CZ_MESSAGE_MAX */
+    uint32_t flags;       /* as cz_frame_desc.flags (low byte) */
+    uint32_t first_sub;   /* index of the run's first cz_fanout_sub */
+    uint32_t count;       /* subscribers; 0 = the run contributes nothing */
+} cz_fanout_run;           /* 40 bytes */
+typedef struct cz_fanout_wave {
+    uint32_t run;   /* index into the run array */
+    uint32_t first; /* the wave's lane 0 serves this subscriber of the run (a multiple of 64) */
+} cz_fanout_wave;
+/* order of the classes in the wave table and in class_count[] */
+#define CZ_FANOUT_LINES 0
+#define CZ_FANOUT_REGION 1
+#define CZ_FANOUT_DIRECT 2
+/* Host-side planner, no device call; d_in and d_out are used as addresses only (alignment class).
+ * Every run is validated before anything is written: len > CZ_MESSAGE_MAX -> CZ_EMSGSIZE;
+ * out_stride < len + 33, first_sub + count past 2^32, out_off + count * out_stride past the
+ * address space, null pointers -> CZ_EINVAL.  *nwaves = sum of ceil(count / 64); a wave_cap below
+ * that (or a null h_waves) returns CZ_EINVAL with *nwaves set and nothing else written, as
+ * cz_plan_segments.  class_count[c] = waves of class c (they sum to *nwaves); *region_stride =
+ * the largest out_stride among the region-class runs (0: none), which sizes that launch's LDS.
+ * Replaces the per-Msg loop of Dist.distribute (zmq/socket/pubsub/Dist.java) -> write(pipe, msg)
+ * -> mechanism.encode, once per message and per pipe. */
+int cz_plan_fanout(const cz_fanout_run *h_runs, uint32_t nruns, const void *d_in, const void *d_out,
+                   cz_fanout_wave *h_waves, uint32_t wave_cap, uint32_t *nwaves, uint32_t class_count[3],
+                   uint32_t *region_stride);
+/* Dist.distribute (zmq/socket/pubsub/Dist.java) -> write(pipe, msg) -> mechanism.encode, once per
+ * message and per pipe: all of it for R messages.  d_runs / d_waves: device copies of the run array
+ * and of the planner's wave table; class_count and region_stride as the planner returned them
+ * (region_stride 0 = the largest region slot, 256).  nruns == 0 or no waves: CZ_OK, nothing
+ * launched.  Null pointers: CZ_EINVAL (checked before the device is touched).  No device: CZ_EHIP;
+ * there is no CPU fallback. */
+int cz_seal_fanout_runs(const cz_fanout_run *d_runs, uint32_t nruns, const cz_fanout_wave *d_waves,
+                        const uint32_t class_count[3], uint32_t region_stride, const void *d_in,
+                        const cz_fanout_sub *d_subs, const void *d_subkeys, void *d_out, void *stream);
+
 /* Synthetic data: fill d_buf with the counter-based SplitMix64 byte stream (seed). */
 int cz_fill(void *d_buf, uint64_t nbytes, uint64_t seed, void *stream);
 /* Measurement: device-to-device copy of nbytes (a multiple of 16) with 16-byte loads and stores,
@@ -386,9 +445,11 @@ int cz_engine_send(cz_engine *e, int conn, const void *payload, uint32_t len, in
  * checked before anything is queued: an unknown or removed id is CZ_EINVAL, an over-long payload
  * CZ_EMSGSIZE, a full arena CZ_ENOMEM, each with nothing queued.  Connections that have failed
  * are skipped (Dist.write drops a pipe it cannot write to); *queued (optional) = frames queued.
- * An id listed twice gets two frames with consecutive nonces.  flush_out seals a publish's run
- * of at least cz_tune("fanout_min") frames with one cz_seal_fanout launch; the wire bytes are
- * those of the same messages queued with cz_engine_send. */
+ * An id listed twice gets two frames with consecutive nonces.  flush_out takes a publish's run
+ * of at least cz_tune("fanout_min") frames -- or of at least 64 frames with a payload of at most
+ * cz_tune("fanout_short") bytes -- out of the segment plan, and seals all such runs of a flush
+ * group with one cz_seal_fanout_runs call; the wire bytes are those of the same messages queued
+ * with cz_engine_send, whichever way the frames are routed. */
 int cz_engine_publish(cz_engine *e, const int *conns, uint32_t nconn, const void *payload, uint32_t len,
                       int msg_flags, uint32_t *queued);
 /* seal every queued Msg on the device and V2-frame it into one pinned output in SEND order
@@ -620,9 +681,17 @@ int cz_device_ok(void);
  *              byte-shifted line emitter (default), 0 = 128-byte groups at each output's base
  *   "open_ina" / "seal_ina": 1 = line paths for bodies / payloads off 16-byte alignment with
  *              dword-aligned loads (default), 0 = lane-wise unaligned paths
- *   "fanout_min": cz_engine_flush_out seals a publish's run of at least this many frames with
- *              cz_seal_fanout (default 2^18: each run is one launch, which must fill the device by itself
- *              to beat the segment plan's one launch per group); 0 = every publish stays on the segment path */
+ *   "fanout_min": cz_engine_flush_out takes a publish's run of at least this many frames out of the
+ *              segment plan, whatever its length; all such runs of a flush group are sealed by one
+ *              cz_seal_fanout_runs call (default 2^18, the count at which one lane per subscriber fills
+ *              the device at 4 KiB); 0 = every publish stays on the segment path
+ *   "fanout_short": ... and so is a run of at least 64 frames (one full wave) whose payload is at most
+ *              this many bytes, unless fanout_min is 0; 0 = rule off.  Default 256, the largest measured
+ *              length at which the grouped call is not slower than the segment kernels at every
+ *              R x N >= 1024 (100 B: 0.0102 against 0.0179 ms for 16 publishes to 1024 subscribers; 256 B:
+ *              0.0150 against 0.0198 ms; 1024 B: 0.0395 against 0.0317 ms, so not 1024) and the routed
+ *              flush of 256 publishes to 1024 connections is not slower than the segment-plan flush
+ *              (100 B: 2.7 against 6.3 ms; 256 B: 3.8 against 5.6 ms); profiles/fanout/fanout_runs.json */
 int cz_tune(const char *key, int value);
 
 #ifdef __cplusplus

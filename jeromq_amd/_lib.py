@@ -88,6 +88,20 @@ class cz_fanout_sub(ctypes.Structure):
 assert ctypes.sizeof(cz_fanout_sub) == 16
 
 
+class cz_fanout_run(ctypes.Structure):
+    _fields_ = [("payload_off", ctypes.c_uint64), ("out_off", ctypes.c_uint64), ("out_stride", ctypes.c_uint64),
+                ("len", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("first_sub", ctypes.c_uint32),
+                ("count", ctypes.c_uint32)]
+
+
+class cz_fanout_wave(ctypes.Structure):
+    _fields_ = [("run", ctypes.c_uint32), ("first", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(cz_fanout_run) == 40 and ctypes.sizeof(cz_fanout_wave) == 8
+CZ_FANOUT_LINES, CZ_FANOUT_REGION, CZ_FANOUT_DIRECT = 0, 1, 2
+
+
 class cz_accept_result(ctypes.Structure):
     _fields_ = [("rc", ctypes.c_int32), ("event", ctypes.c_int32), ("slot", ctypes.c_int32),
                 ("reply_len", ctypes.c_uint32)]
@@ -113,6 +127,9 @@ SIGNATURES = {
     "cz_seal_uniform_box": (_I, [_U32, _U32, _VP, _U64, _VP, _U64, _VP, _U64, _VP]),
     "cz_open_uniform": (_I, [_U32, _U32, _VP, _U64, _VP, _U64, _VP, _U64, _I, _VP, _VP]),
     "cz_seal_fanout": (_I, [_U32, _U32, _VP, _U32, _VP, _VP, _VP, _U64, _VP]),
+    "cz_plan_fanout": (_I, [_VP, _U32, _VP, _VP, _VP, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32),
+                            ctypes.POINTER(_U32)]),
+    "cz_seal_fanout_runs": (_I, [_VP, _U32, _VP, ctypes.POINTER(_U32), _U32, _VP, _VP, _VP, _VP, _VP]),
     "cz_plan_order": (_I, [_VP, _U32, _VP]),
     "cz_plan_segments": (_I, [_VP, _U32, _I, _U32, _VP, _U32, ctypes.POINTER(_U32), _VP, _U32,
                               ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),

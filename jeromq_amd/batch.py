@@ -83,6 +83,71 @@ def seal_fanout(payload, length, flags, subs, subkeys_t, out, out_stride, count,
                                          out_stride, _stream(stream)), "cz_seal_fanout")
 
 
+FANOUT_RUN_DTYPE = np.dtype([("payload_off", "<u8"), ("out_off", "<u8"), ("out_stride", "<u8"), ("len", "<u4"),
+                             ("flags", "<u4"), ("first_sub", "<u4"), ("count", "<u4")])
+FANOUT_WAVE_DTYPE = np.dtype([("run", "<u4"), ("first", "<u4")])
+
+
+class FanoutPlan:
+    """Host plan of a grouped fan-out (cz_plan_fanout): `waves` (FANOUT_WAVE_DTYPE) sorted by staging
+    class, `class_count` = waves of the line / region / lane-wise class, `region_stride` = what sizes
+    the region launch's LDS.  `to(device)` uploads the run and wave tables."""
+
+    def __init__(self, runs_np, waves, class_count, region_stride):
+        self.runs, self.waves = runs_np, waves
+        self.class_count, self.region_stride = list(class_count), region_stride
+        self.nruns, self.nwaves = len(runs_np), len(waves)
+        self.d_runs = self.d_waves = None
+
+    def to(self, device):
+        import torch
+        self.d_runs = torch.from_numpy(np.ascontiguousarray(self.runs).view(np.uint8).copy()).to(device)
+        self.d_waves = torch.from_numpy(np.ascontiguousarray(self.waves).view(np.uint8).copy()).to(device)
+        return self
+
+
+def plan_fanout(runs_np, inp, out):
+    """Plan the grouped fan-out of `runs_np` (FANOUT_RUN_DTYPE) reading `inp` and writing `out`: device
+    tensors (or plain addresses), used for their 16-byte alignment only.  Returns a FanoutPlan."""
+    r = np.ascontiguousarray(runs_np, dtype=FANOUT_RUN_DTYPE)
+    a_in, a_out = (t if isinstance(t, int) else t.data_ptr() for t in (inp, out))
+    nw, rs, cc = ctypes.c_uint32(), ctypes.c_uint32(), (ctypes.c_uint32 * 3)()
+    L = _lib.lib()
+    L.cz_plan_fanout(r.ctypes.data, len(r), a_in, a_out, None, 0, ctypes.byref(nw), cc, ctypes.byref(rs))
+    waves = np.zeros(max(nw.value, 1), dtype=FANOUT_WAVE_DTYPE)
+    _lib.check(L.cz_plan_fanout(r.ctypes.data, len(r), a_in, a_out, waves.ctypes.data, len(waves), ctypes.byref(nw),
+                                cc, ctypes.byref(rs)), "cz_plan_fanout")
+    return FanoutPlan(r, waves[:nw.value], cc, rs.value)
+
+
+def seal_fanout_runs(plan, inp, subs, subkeys_t, out, stream=None):
+    """Grouped PUB fan-out: every run of `plan` (plan_fanout(...).to(device)) sealed in one call of at
+    most three launches; run r writes what seal_fanout writes for it alone.  The runs' output ranges
+    must not overlap.  Bounds are checked against the plan's host copy of the runs."""
+    _need_cuda_u8(inp, "in")
+    _need_cuda_u8(out, "out")
+    _need_cuda_u8(subkeys_t, "subkeys")
+    if subs is None or not subs.is_cuda:
+        raise ValueError("subs must be a CUDA (HIP) tensor")
+    if plan.nruns and plan.d_runs is None:
+        raise ValueError("plan not uploaded: plan.to(device)")
+    live = plan.runs[plan.runs["count"] > 0]
+    if len(live):
+        ln, cnt = live["len"].astype(np.uint64), live["count"].astype(np.uint64)
+        nsubs = subs.numel() * subs.element_size() // FANOUT_SUB_DTYPE.itemsize
+        st = live["out_stride"]
+        owns = ((st % 128 == 0) & (st < (1 << 25))) | ((st % 16 == 0) & (st <= 256))   # whole slots are written
+        last = np.where(owns, st, ln + np.uint64(33))
+        if (np.any(live["payload_off"] + ln > np.uint64(inp.numel()))
+                or np.any(live["out_off"] + (cnt - np.uint64(1)) * st + last > np.uint64(out.numel()))
+                or np.any(live["first_sub"].astype(np.uint64) + cnt > np.uint64(nsubs))):
+            raise ValueError("run out of bounds")
+    cc = (ctypes.c_uint32 * 3)(*plan.class_count)
+    _lib.check(_lib.lib().cz_seal_fanout_runs(_ptr(plan.d_runs), plan.nruns, _ptr(plan.d_waves), cc,
+                                              plan.region_stride, _ptr(inp), _ptr(subs), _ptr(subkeys_t), _ptr(out),
+                                              _stream(stream)), "cz_seal_fanout_runs")
+
+
 def seal_uniform_box(box, box_stride, out, out_stride, count, length, subkey, counter0, stream=None):
     """Uniform seal from the reference's box layout: slot i of `box` holds 0^32 || flags ||
     payload (length = payload bytes), as CurveClientMechanism.encode hands it to Curve.afternm."""

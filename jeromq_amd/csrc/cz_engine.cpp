@@ -183,16 +183,18 @@ struct OutMsg {
     uint32_t pub = 0;  // cz_engine_publish call this frame belongs to (0: cz_engine_send)
 };
 
-// A run of one publish's frames inside a flush group, sealed by one cz_seal_fanout launch:
-// send-order frames [first, first + count) share payload, length and flags, and their body slots
-// are contiguous at one stride.
+// A run of one publish's frames inside a flush group, one cz_fanout_run of the group's
+// cz_seal_fanout_runs call: send-order frames [first, first + count) share payload, length and
+// flags, and their body slots are contiguous at one stride.
 struct FanRun {
     uint32_t first, count;
 };
 
 // The fan-out runs of pend[fa, fb): maximal runs of consecutive frames of one publish with at
-// least `min_run` frames (0: none).
-void fanout_runs(const std::vector<OutMsg> &pend, uint32_t fa, uint32_t fb, uint32_t min_run, std::vector<FanRun> &runs)
+// least `min_run` frames, or with at least one full wave of frames and a payload of at most
+// `short_len` bytes (0: that rule off).  min_run 0: none.
+void fanout_runs(const std::vector<OutMsg> &pend, uint32_t fa, uint32_t fb, uint32_t min_run, uint32_t short_len,
+                 std::vector<FanRun> &runs)
 {
     runs.clear();
     if (min_run == 0)
@@ -202,7 +204,7 @@ void fanout_runs(const std::vector<OutMsg> &pend, uint32_t fa, uint32_t fb, uint
         if (pend[i].pub)
             while (j < fb && pend[j].pub == pend[i].pub)
                 j++;
-        if (pend[i].pub && j - i >= min_run)
+        if (pend[i].pub && (j - i >= min_run || (short_len && j - i >= 64u && pend[i].len <= short_len)))
             runs.push_back({i, j - i});
         i = j;
     }
@@ -255,7 +257,8 @@ struct cz_engine {
     HostBuf h_plain;
     std::vector<InMsg> in_msgs;
     // device staging (grows, never shrinks)
-    DevBuf d_in, d_body, d_wire, d_desc, d_seg, d_comb, d_work, d_items, d_status, d_nonces, d_plain, d_subs;
+    DevBuf d_in, d_body, d_wire, d_desc, d_seg, d_comb, d_work, d_items, d_status, d_nonces, d_plain, d_subs,
+        d_fruns, d_fwaves;  // grouped fan-out: run and wave tables
     uint32_t pub_seq = 0;  // id of the last cz_engine_publish call (OutMsg::pub)
     HostBuf h_status, h_nonces;
     HostBuf h_meta;  // pinned staging of descriptors / items / segment lists (async H2D)
@@ -285,7 +288,7 @@ struct cz_engine {
                 (void)hipStreamDestroy(q);
             }
         for (DevBuf *b : {&subkeys, &d_in, &d_body, &d_wire, &d_desc, &d_seg, &d_comb, &d_work, &d_items, &d_status,
-                          &d_nonces, &d_plain, &d_subs})
+                          &d_nonces, &d_plain, &d_subs, &d_fruns, &d_fwaves})
             b->release();
         for (HostBuf *b : {&arena, &h_wire, &h_plain, &h_status, &h_nonces, &h_meta})
             b->release();
@@ -379,18 +382,24 @@ struct cz_engine {
                 }
         }
         // publishes: inside a group, a run of one publish's frames has contiguous body slots of
-        // one stride (slots follow send order) and leaves the segment plan for one cz_seal_fanout
-        // launch; a publish split by a group edge is two runs.  fan[i]: frame i is in such a run.
+        // one stride (slots follow send order) and leaves the segment plan for the group's one
+        // cz_seal_fanout_runs call; a publish split by a group edge is two runs.  fan[i]: frame i
+        // is in such a run.  roff / fwoff: the groups' ranges in the run and wave tables.
         std::vector<std::vector<FanRun>> fruns(groups.size());
         std::vector<uint8_t> fan(n, 0);
-        bool any_fan = false;
+        std::vector<uint64_t> roff(groups.size() + 1, 0), fwoff(groups.size() + 1, 0);
+        const uint32_t fan_min = fanout_min(), fan_short = fanout_short();
         for (size_t gi = 0; gi < groups.size(); gi++) {
-            fanout_runs(pend, groups[gi].fa, groups[gi].fb, fanout_min(), fruns[gi]);
+            fanout_runs(pend, groups[gi].fa, groups[gi].fb, fan_min, fan_short, fruns[gi]);
+            roff[gi + 1] = roff[gi] + fruns[gi].size();
+            fwoff[gi + 1] = fwoff[gi];
             for (const FanRun &r : fruns[gi]) {
                 std::fill(fan.begin() + r.first, fan.begin() + r.first + r.count, (uint8_t)1);
-                any_fan = true;
+                fwoff[gi + 1] += ((uint64_t)r.count + 63) / 64;
             }
         }
+        const uint64_t nfrun = roff[groups.size()], nfwave = fwoff[groups.size()];
+        const bool any_fan = nfrun != 0;
         std::vector<uint64_t> soff(groups.size() + 1, 0), coff(groups.size() + 1, 0), woff(groups.size() + 1, 0);
         uint64_t slot = 0, hi = 0;
         for (size_t gi = 0; gi < groups.size(); gi++) {
@@ -413,7 +422,9 @@ struct cz_engine {
         const uint64_t m_items = 0, m_desc = (uint64_t)n * sizeof(cz_v2_item),
                        m_seg = m_desc + (uint64_t)n * sizeof(cz_frame_desc), m_comb = m_seg + nseg * sizeof(cz_segment),
                        m_subs = m_comb + ncomb * sizeof(cz_combine),
-                       m_end = m_subs + (any_fan ? (uint64_t)n * sizeof(cz_fanout_sub) : 0);
+                       m_fruns = m_subs + (any_fan ? (uint64_t)n * sizeof(cz_fanout_sub) : 0),
+                       m_fwaves = m_fruns + nfrun * sizeof(cz_fanout_run),
+                       m_end = m_fwaves + nfwave * sizeof(cz_fanout_wave);
         hipError_t e;
         if ((e = d_in.reserve(std::max<uint64_t>(arena_used, 16))) != hipSuccess ||
             (e = d_body.reserve(slot)) != hipSuccess || (e = d_wire.reserve(wire_total)) != hipSuccess ||
@@ -422,7 +433,9 @@ struct cz_engine {
             (e = d_seg.reserve(std::max<uint64_t>(nseg, 1) * sizeof(cz_segment))) != hipSuccess ||
             (e = d_comb.reserve(std::max<uint64_t>(ncomb, 1) * sizeof(cz_combine))) != hipSuccess ||
             (e = d_work.reserve(std::max<uint64_t>(npart, 1) * 64)) != hipSuccess ||
-            (any_fan && (e = d_subs.reserve((uint64_t)n * sizeof(cz_fanout_sub))) != hipSuccess) ||
+            (any_fan && ((e = d_subs.reserve((uint64_t)n * sizeof(cz_fanout_sub))) != hipSuccess ||
+                         (e = d_fruns.reserve(nfrun * sizeof(cz_fanout_run))) != hipSuccess ||
+                         (e = d_fwaves.reserve(nfwave * sizeof(cz_fanout_wave))) != hipSuccess)) ||
             (e = h_wire.reserve(wire_total)) != hipSuccess || (e = h_meta.reserve(m_end)) != hipSuccess)
             return hip_fail(e, "cz_engine: alloc");
         // descriptors and items are built straight into pinned staging (pageable sources would
@@ -431,6 +444,8 @@ struct cz_engine {
         cz_v2_item *h_items = (cz_v2_item *)(hm + m_items);
         cz_frame_desc *h_desc = (cz_frame_desc *)(hm + m_desc);
         cz_fanout_sub *h_subs = (cz_fanout_sub *)(hm + m_subs);  // by send index, fan-out frames only
+        cz_fanout_run *h_fruns = (cz_fanout_run *)(hm + m_fruns);
+        cz_fanout_wave *h_fwaves = (cz_fanout_wave *)(hm + m_fwaves);
         pt.mark("plan");
         std::vector<hipEvent_t> ev(groups.size(), nullptr), evk(groups.size(), nullptr);
         EvGuard evguard{ev}, evkguard{evk};
@@ -478,6 +493,20 @@ struct cz_engine {
             // one copy for the group's subscriber records: first run's start to last run's end
             const uint32_t sub_a = fr.empty() ? 0u : fr.front().first,
                            sub_b = fr.empty() ? 0u : fr.back().first + fr.back().count;
+            // the group's run table (a run's first_sub is its send index) and wave table
+            const uint32_t gfr = (uint32_t)fr.size(), gfw = (uint32_t)(fwoff[gi + 1] - fwoff[gi]);
+            cz_fanout_run *hr = h_fruns + roff[gi];
+            uint32_t fclass[3] = {0, 0, 0}, fregion = 0;
+            for (uint32_t k = 0; k < gfr; k++) {
+                const OutMsg &m = pend[fr[k].first];
+                hr[k] = {m.arena_off, h_items[fr[k].first].src_off,
+                         round_up((uint64_t)m.len + CZ_MESSAGE_OVERHEAD, SLOT_ALIGN), m.len, m.flags & 0xffu,
+                         fr[k].first, fr[k].count};
+            }
+            if (gfr)
+                fregion = plan_fanout(hr, gfr, d_in.ptr, d_body.ptr, h_fwaves + fwoff[gi], fclass);
+            const cz_fanout_run *dfr = (const cz_fanout_run *)d_fruns.ptr + roff[gi];
+            const cz_fanout_wave *dfw = (const cz_fanout_wave *)d_fwaves.ptr + fwoff[gi];
             plan_segments(h_desc + g.fa, gd, 0, seg, sg.seg, sg.comb, sg.npart);
             const uint32_t gseg = (uint32_t)sg.seg.size(), gcomb = (uint32_t)sg.comb.size();
             if (gseg != soff[gi + 1] - soff[gi] || gcomb != coff[gi + 1] - coff[gi] || sg.npart != woff[gi + 1] - woff[gi])
@@ -496,7 +525,11 @@ struct cz_engine {
                 (sub_b > sub_a && (e = hipMemcpyAsync((cz_fanout_sub *)d_subs.ptr + sub_a, h_subs + sub_a,
                                                       (uint64_t)(sub_b - sub_a) * sizeof(cz_fanout_sub),
                                                       hipMemcpyHostToDevice, qh)) != hipSuccess) ||
-                (gseg && (e = hipMemcpyAsync(dsg, (const cz_segment *)(hm + m_seg) + soff[gi],
+                (gfr && ((e = hipMemcpyAsync((void *)dfr, hr, (uint64_t)gfr * sizeof(cz_fanout_run), hipMemcpyHostToDevice,
+                                             qh)) != hipSuccess ||
+                         (e = hipMemcpyAsync((void *)dfw, h_fwaves + fwoff[gi], (uint64_t)gfw * sizeof(cz_fanout_wave),
+                                             hipMemcpyHostToDevice, qh)) != hipSuccess)) ||
+                (gseg &&(e = hipMemcpyAsync(dsg, (const cz_segment *)(hm + m_seg) + soff[gi],
                                              (uint64_t)gseg * sizeof(cz_segment), hipMemcpyHostToDevice, qh)) !=
                              hipSuccess) ||
                 (gcomb && (e = hipMemcpyAsync(dcb, (const cz_combine *)(hm + m_comb) + coff[gi],
@@ -509,16 +542,10 @@ struct cz_engine {
             //     wire positions; (c) D2H stream: the group's wire bytes back
             if (qh != qk && (e = hipStreamWaitEvent(qk, ev[gi], 0)) != hipSuccess)
                 return hip_fail(e, "cz_engine: flush_out");
-            for (const FanRun &r : fr) {
-                const OutMsg &m = pend[r.first];
-                if ((e = czk_seal_fanout((const uint8_t *)d_in.ptr + m.arena_off, m.len, m.flags & 0xffu,
-                                         (const cz_fanout_sub *)d_subs.ptr + r.first, subkeys.ptr,
-                                         (uint8_t *)d_body.ptr + h_items[r.first].src_off,
-                                         round_up((uint64_t)m.len + CZ_MESSAGE_OVERHEAD, SLOT_ALIGN), r.count, qk)) !=
-                    hipSuccess)
-                    return hip_fail(e, "cz_engine: flush_out fan-out");
-            }
-            if ((gseg && (e = czk_seal_segments(dd, dsg, gseg, dcb, gcomb, d_in.ptr, d_body.ptr, subkeys.ptr,
+            if (gfr && (e = czk_seal_fanout_runs(dfr, dfw, fclass, fregion, d_in.ptr, (const cz_fanout_sub *)d_subs.ptr,
+                                                 subkeys.ptr, d_body.ptr, qk)) != hipSuccess)
+                return hip_fail(e, "cz_engine: flush_out fan-out");
+            if ((gseg &&(e = czk_seal_segments(dd, dsg, gseg, dcb, gcomb, d_in.ptr, d_body.ptr, subkeys.ptr,
                                                 (uint8_t *)d_work.ptr + 64 * woff[gi], qk)) != hipSuccess) ||
                 (e = czk_v2_copy((const cz_v2_item *)d_items.ptr + g.fa, gn, d_body.ptr, d_wire.ptr, qk)) !=
                     hipSuccess ||

@@ -254,16 +254,32 @@ uint64_t nacl_one_bytes()
     return std::max<uint64_t>(g_nacl_one_bytes.load(std::memory_order_relaxed), czk_nacl_one_max());
 }
 
-// cz_engine_flush_out: a publish's run of at least this many frames leaves the segment plan for one
-// cz_seal_fanout launch; 0 = never (cz_tune "fanout_min").  Each run is a launch of its own on the
-// group's stream, so a run pays off only when it fills the device by itself: a launch of up to
-// 16 384 x 4 KiB lanes takes the 0.13 ms one lane needs for its 65 blocks, and 256 publishes to
-// 1024 connections flushed 2.3x slower routed than in the segment plan, whose one launch per group
-// holds every frame ("PUB fan-out").  2^18 is the smallest measured count at
-// which the run's own launch is throughput-bound and ahead of the segment kernels.
+// cz_engine_flush_out: a publish's run of at least this many frames leaves the segment plan, whatever
+// its length, for the group's cz_seal_fanout_runs call; 0 = never (cz_tune "fanout_min").  One lane
+// per subscriber keeps a frame on one lane: up to 16 384 x 4 KiB lanes take the 0.13 ms one lane needs
+// for its 65 blocks, where the segment plan spreads them ("PUB fan-out").  2^18
+// is the smallest measured count at which such a launch is throughput-bound and ahead of the segment
+// kernels at 4 KiB.
 static std::atomic<uint32_t> g_fanout_min{1u << 18};
 
 uint32_t fanout_min() { return g_fanout_min.load(std::memory_order_relaxed); }
+
+// cz_engine_flush_out: a publish's run of at least 64 frames (one full wave) whose payload is at most
+// this many bytes also leaves the segment plan, unless fanout_min is 0; 0 = rule off (cz_tune
+// "fanout_short").  All the runs of a flush group are one cz_seal_fanout_runs call.
+// Default 256: the largest measured length (of 100, 256, 1024, 4096) at which the grouped call (d) is
+// not slower than the segment kernels at the flush's own segment length (b') at every measured
+// R x N >= 1024, and the flush routed by it is not slower than the segment-plan flush
+// (tools/fanout_bench.py --runs, profiles/fanout/fanout_runs.json, medians of 7, legs interleaved):
+//   len   (d) / (b') ms at R x N = 1024, 16 384, 262 144              256 x publish to 1024, flush ms
+//   100   0.0095 / 0.0169   0.0102 / 0.0179   0.0297 / 0.0472         2.66 routed, 6.27 segment plan
+//   256   0.0142 / 0.0167   0.0150 / 0.0198   0.0458 / 0.0631         3.76 routed, 5.59 segment plan
+//   1024  0.0382 / 0.0210   0.0395 / 0.0317   0.1522 / 0.1641  (loses below 2^18 lanes; flush 7.57 / 9.33)
+//   4096  0.1331 / 0.0362   0.1368 / 0.0635   0.5998 / 0.5764  (loses everywhere; flush 21.4 / 22.1)
+// Above a few blocks one lane per subscriber is held to that lane's serial walk.
+static std::atomic<uint32_t> g_fanout_short{256};
+
+uint32_t fanout_short() { return g_fanout_short.load(std::memory_order_relaxed); }
 
 // NaCl box/open of one message on the device.  A MESSAGE is the NaCl box of
 // 0^32 || flags || payload, so m[32] rides as the flags byte and m[33:] as the payload; for open
@@ -464,6 +480,46 @@ void plan_segments(const cz_frame_desc *h_desc, uint32_t count, int open, uint32
     npart = parts;
 }
 
+uint64_t fanout_waves(const cz_fanout_run *runs, uint32_t nruns)
+{
+    uint64_t n = 0;
+    for (uint32_t r = 0; r < nruns; r++)
+        n += ((uint64_t)runs[r].count + 63) / 64;
+    return n;
+}
+
+// Grouped fan-out: every run padded to whole waves; a full wave takes its run's staging class
+// (czk_fanout_class: what czk_seal_fanout picks for the run alone), a partial last wave stores
+// lane-wise whatever the class, so it rides in the launch without LDS.  Waves sorted by class, then
+// longest payload first (stable: run order, then wave order), as the segment planner sorts, so a
+// long run does not start last.
+uint32_t plan_fanout(const cz_fanout_run *runs, uint32_t nruns, const void *d_in, const void *d_out, cz_fanout_wave *waves,
+                     uint32_t class_count[3])
+{
+    std::vector<uint32_t> order(nruns);
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [runs](uint32_t a, uint32_t b) { return runs[a].len > runs[b].len; });
+    std::vector<int> cls(nruns);
+    uint32_t region_stride = 0;
+    class_count[0] = class_count[1] = class_count[2] = 0;
+    for (uint32_t r = 0; r < nruns; r++) {
+        const cz_fanout_run &f = runs[r];
+        const bool al = ((((uintptr_t)d_in + f.payload_off) | ((uintptr_t)d_out + f.out_off) | f.out_stride) & 15u) == 0;
+        cls[r] = czk_fanout_class(f.out_stride, f.len, f.count, al ? 1 : 0);
+        class_count[cls[r]] += f.count / 64;
+        class_count[CZ_FANOUT_DIRECT] += f.count % 64 ? 1u : 0u;
+        if (cls[r] == CZ_FANOUT_REGION)
+            region_stride = std::max(region_stride, (uint32_t)f.out_stride);
+    }
+    uint32_t at[3] = {0, class_count[0], class_count[0] + class_count[1]};
+    for (uint32_t r : order) {
+        const uint32_t count = runs[r].count;
+        for (uint64_t first = 0; first < count; first += 64)
+            waves[at[first + 64 <= count ? cls[r] : CZ_FANOUT_DIRECT]++] = {r, (uint32_t)first};
+    }
+    return region_stride;
+}
+
 }  // namespace czi
 
 using namespace czi;
@@ -505,6 +561,11 @@ int cz_tune(const char *key, int value)
     if (key && strcmp(key, "fanout_min") == 0) {
         const int old = (int)g_fanout_min.load(std::memory_order_relaxed);
         g_fanout_min.store((uint32_t)std::max(value, 0), std::memory_order_relaxed);
+        return old;
+    }
+    if (key && strcmp(key, "fanout_short") == 0) {
+        const int old = (int)g_fanout_short.load(std::memory_order_relaxed);
+        g_fanout_short.store((uint32_t)std::max(value, 0), std::memory_order_relaxed);
         return old;
     }
     int old = czk_tune(key, value);
@@ -644,6 +705,54 @@ int cz_seal_fanout(uint32_t count, uint32_t len, const void *d_payload, uint32_t
     hipError_t e = czk_seal_fanout(d_payload, len, flags, d_subs, d_subkeys, d_out, out_stride, count,
                                    (hipStream_t)stream);
     return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_seal_fanout");
+}
+
+int cz_plan_fanout(const cz_fanout_run *h_runs, uint32_t nruns, const void *d_in, const void *d_out,
+                   cz_fanout_wave *h_waves, uint32_t wave_cap, uint32_t *nwaves, uint32_t class_count[3],
+                   uint32_t *region_stride)
+{
+    if ((nruns && (!h_runs || !d_in || !d_out)) || !nwaves || !class_count || !region_stride)
+        return fail(CZ_EINVAL, "cz_plan_fanout: null pointer");
+    for (uint32_t r = 0; r < nruns; r++) {
+        const cz_fanout_run &f = h_runs[r];
+        uint64_t span = 0;
+        if (f.len > (uint32_t)CZ_MESSAGE_MAX)
+            return fail(CZ_EMSGSIZE, "cz_plan_fanout: run %u: %u-byte payload exceeds CZ_MESSAGE_MAX", r, f.len);
+        if (f.out_stride < (uint64_t)f.len + CZ_MESSAGE_OVERHEAD)
+            return fail(CZ_EINVAL, "cz_plan_fanout: run %u: out_stride smaller than the body", r);
+        if ((uint64_t)f.first_sub + f.count > 0xffffffffull)
+            return fail(CZ_EINVAL, "cz_plan_fanout: run %u: first_sub + count overflows", r);
+        // (the whole slots of an owning run, as uniform_span: within a 2^47-byte address range)
+        if (__builtin_mul_overflow((uint64_t)f.count, f.out_stride, &span) ||
+            __builtin_add_overflow(span, f.out_off, &span) || span > (1ull << 47))
+            return fail(CZ_EINVAL, "cz_plan_fanout: run %u: out_off + count x out_stride overflows the address space", r);
+    }
+    const uint64_t need = fanout_waves(h_runs, nruns);
+    if (need > 0xffffffffull)
+        return fail(CZ_EINVAL, "cz_plan_fanout: more than 2^32 waves");
+    *nwaves = (uint32_t)need;
+    if (need > wave_cap || (need && !h_waves))
+        return fail(CZ_EINVAL, "cz_plan_fanout: capacity too small (need %u waves)", *nwaves);
+    *region_stride = plan_fanout(h_runs, nruns, d_in, d_out, h_waves, class_count);
+    return CZ_OK;
+}
+
+int cz_seal_fanout_runs(const cz_fanout_run *d_runs, uint32_t nruns, const cz_fanout_wave *d_waves,
+                        const uint32_t class_count[3], uint32_t region_stride, const void *d_in,
+                        const cz_fanout_sub *d_subs, const void *d_subkeys, void *d_out, void *stream)
+{
+    if (!class_count)
+        return fail(CZ_EINVAL, "cz_seal_fanout_runs: null pointer");
+    const uint64_t nwaves = (uint64_t)class_count[0] + class_count[1] + class_count[2];
+    if (nruns == 0 || nwaves == 0)
+        return CZ_OK;
+    if (!d_runs || !d_waves || !d_in || !d_subs || !d_subkeys || !d_out)
+        return fail(CZ_EINVAL, "cz_seal_fanout_runs: null pointer");
+    if (nwaves > 0xffffffffull)
+        return fail(CZ_EINVAL, "cz_seal_fanout_runs: more than 2^32 waves");
+    hipError_t e = czk_seal_fanout_runs(d_runs, d_waves, class_count, region_stride, d_in, d_subs, d_subkeys, d_out,
+                                        (hipStream_t)stream);
+    return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_seal_fanout_runs");
 }
 
 int cz_seal_uniform_box(uint32_t count, uint32_t len, const void *d_box, uint64_t box_stride, void *d_out,

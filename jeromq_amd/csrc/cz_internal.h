@@ -19,6 +19,9 @@ hipError_t czk_open_desc(const cz_frame_desc *, const uint32_t *, uint32_t, cons
                          uint16_t *, uint64_t *, hipStream_t);
 hipError_t czk_seal_fanout(const void *, uint32_t, uint32_t, const cz_fanout_sub *, const void *, void *, uint64_t,
                            uint32_t, hipStream_t);
+int czk_fanout_class(uint64_t, uint32_t, uint32_t, int);
+hipError_t czk_seal_fanout_runs(const cz_fanout_run *, const cz_fanout_wave *, const uint32_t *, uint32_t, const void *,
+                                const cz_fanout_sub *, const void *, void *, hipStream_t);
 hipError_t czk_subkeys(const void *, void *, uint32_t, const uint8_t *, hipStream_t);
 hipError_t czk_seal_segments(const cz_frame_desc *, const cz_segment *, uint32_t, const cz_combine *, uint32_t,
                              const void *, void *, const void *, void *, hipStream_t);
@@ -36,10 +39,18 @@ int fail(int code, const char *fmt, ...);
 int hs_thread_init();  // the calling thread's handshake context (cz_handshake.cpp)
 uint64_t nacl_one_bytes();  // boxes up to this size take k_nacl_one (cz_tune "nacl_one_max")
 uint32_t fanout_min();      // publish runs of at least this many frames take k_seal_fanout (cz_tune "fanout_min")
+uint32_t fanout_short();    // ... and runs of a full wave or more with payloads up to this (cz_tune "fanout_short")
 int hip_fail(hipError_t e, const char *where);
 const uint8_t *prefix_for(int direction);
 void plan_segments(const cz_frame_desc *h_desc, uint32_t count, int open, uint32_t seg_blocks,
                    std::vector<cz_segment> &segs, std::vector<cz_combine> &combs, uint32_t &npart);
+
+// The wave table of a grouped fan-out (cz_plan_fanout) for runs already validated: waves[0, nwaves) sorted by
+// class (CZ_FANOUT_LINES, _REGION, _DIRECT), longest payload first inside a class; returns the largest region stride.
+// `waves` must hold fanout_waves(runs, nruns) records.
+uint64_t fanout_waves(const cz_fanout_run *runs, uint32_t nruns);
+uint32_t plan_fanout(const cz_fanout_run *runs, uint32_t nruns, const void *d_in, const void *d_out, cz_fanout_wave *waves,
+                     uint32_t class_count[3]);
 
 // segments, combine records and partial records the planner makes for one frame of `len` (payload for seal, body
 // for open) -- lets a caller size its buffers before planning

@@ -2690,21 +2690,28 @@ __device__ __forceinline__ const uint8_t *per_lane_ptr(const uint8_t *p)
 #else
 #define CZ_FANOUT_SRC(p) (p)
 #endif
+// One wave of one fan-out run (k_seal_fanout: the launch is the run; k_seal_fanout_runs: the wave's
+// run record).  Lane `lane` serves subscriber i = wave_first + lane of the run's `count`, subs and
+// out being the run's first record and first slot.  `staged`: the run passes the launcher's checks
+// for this instantiation's emitter (czk_seal_fanout); a wave that does not, or is not full, stores
+// lane-wise.  region_part16: the wave's LDS partition of the region emitter, in 16-byte units.
+// No workgroup barrier: the waves of a workgroup may serve different runs or have returned.
 template <int ST, bool PAIR>
-__global__ __launch_bounds__(BLOCK) CZ_OCC CZ_OPEN_UNI_OCC void k_seal_fanout(
-    const uint8_t *__restrict__ payload, uint32_t len, uint32_t flags, const cz_fanout_sub *__restrict__ subs,
-    const uint8_t *__restrict__ subkeys, uint8_t *__restrict__ out, uint64_t out_stride, uint32_t count, int owns)
+__device__ __forceinline__ void seal_fanout_wave(const uint8_t *__restrict__ payload, uint32_t len, uint32_t flags,
+                                                 const cz_fanout_sub *__restrict__ subs,
+                                                 const uint8_t *__restrict__ subkeys, uint8_t *__restrict__ out,
+                                                 uint64_t out_stride, uint32_t count, int owns, uint32_t wave_first,
+                                                 bool staged, u32 region_part16)
 {
     extern __shared__ uint4 smem[];
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    const uint32_t wave_first = i & ~63u;
+    const uint32_t i = wave_first + (threadIdx.x & 63u);
     if (wave_first >= count)
         return;
     const bool full_wave = wave_first + 64u <= count;
     const u32 mlen = len + 33u;
     const u32 fl = flags & 0xffu;
     const uint8_t *src = CZ_FANOUT_SRC(payload);
-    if (ST != ST_DIRECT && full_wave) {
+    if (ST != ST_DIRECT && full_wave && staged) {
         const cz_fanout_sub sb = subs[i];
         u32 key[8];
         load_key(subkeys + 32ull * sb.key_idx, key);
@@ -2722,7 +2729,7 @@ __global__ __launch_bounds__(BLOCK) CZ_OCC CZ_OPEN_UNI_OCC void k_seal_fanout(
                 zero_bytes(dst + body_lines, (u32)(out_stride - body_lines));
         } else {
             const u32 st = (u32)out_stride;
-            EmitRegionSeal em{smem + (threadIdx.x >> 6) * ((64u * st) >> 4), out + (uint64_t)wave_first * out_stride, st,
+            EmitRegionSeal em{smem + (threadIdx.x >> 6) * region_part16, out + (uint64_t)wave_first * out_stride, st,
                               lane, mlen};
             seal_frame<MODE_ZMQ, true, EmitRegionSeal, PAIR, false, true, 16>(src, len, fl, sb.counter, key, em);
         }
@@ -2746,6 +2753,53 @@ __global__ __launch_bounds__(BLOCK) CZ_OCC CZ_OPEN_UNI_OCC void k_seal_fanout(
     }
     if (owns && out_stride > mlen)
         zero_bytes(dst + mlen, (u32)(out_stride - mlen));
+}
+
+template <int ST, bool PAIR>
+__global__ __launch_bounds__(BLOCK) CZ_OCC CZ_OPEN_UNI_OCC void k_seal_fanout(
+    const uint8_t *__restrict__ payload, uint32_t len, uint32_t flags, const cz_fanout_sub *__restrict__ subs,
+    const uint8_t *__restrict__ subkeys, uint8_t *__restrict__ out, uint64_t out_stride, uint32_t count, int owns)
+{
+    // (the launcher picked ST for this run: every full wave is staged)
+    seal_fanout_wave<ST, PAIR>(payload, len, flags, subs, subkeys, out, out_stride, count, owns,
+                               (blockIdx.x * BLOCK + threadIdx.x) & ~63u, true, (64u * (u32)out_stride) >> 4);
+}
+
+// The output-ownership rule of a fan-out run (header section 3c), by its stride alone.
+__host__ __device__ __forceinline__ bool fanout_owns(uint64_t out_stride)
+{
+    return (out_stride % 128 == 0 && out_stride < (1ull << 25)) || (out_stride % 16 == 0 && 64 * out_stride <= REGION_MAX);
+}
+
+// Every fan-out run of a flush group in one launch per staging class (cz_seal_fanout_runs): wave w
+// of this launch's slice of the wave table serves subscribers [first, first + 64) of run
+// waves[w].run, writing exactly what k_seal_fanout writes for that run alone.  The wave index goes
+// through readfirstlane, so the wave and run records are scalar loads and payload, subs and out
+// are wave-uniform (the payload off 16-byte alignment is read through per_lane_ptr, as above).
+// The slice's class is a performance choice only: a wave is staged when ITS run passes
+// czk_seal_fanout's checks for this instantiation's emitter -- at least one full wave, payload,
+// output and stride 16-byte aligned, the stride limits, and for the region emitter 64 slots within
+// the wave's fixed LDS partition (region_part16 x 16 bytes) -- and stores lane-wise otherwise.
+template <int ST, bool PAIR>
+__global__ __launch_bounds__(BLOCK) CZ_OCC CZ_OPEN_UNI_OCC void k_seal_fanout_runs(
+    const cz_fanout_run *__restrict__ runs, const cz_fanout_wave *__restrict__ waves, uint32_t nwaves,
+    const uint8_t *__restrict__ in, const cz_fanout_sub *__restrict__ subs, const uint8_t *__restrict__ subkeys,
+    uint8_t *__restrict__ out, uint32_t region_part16)
+{
+    const u32 w = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES + (threadIdx.x >> 6));
+    if (w >= nwaves)
+        return;
+    const cz_fanout_wave wv = waves[w];
+    const cz_fanout_run r = runs[wv.run];
+    const uint8_t *payload = in + r.payload_off;
+    uint8_t *o = out + r.out_off;
+    bool staged = r.count >= 64u && ((((uintptr_t)payload | (uintptr_t)o | r.out_stride) & 15u) == 0);
+    if constexpr (ST == ST_LINES)
+        staged = staged && r.out_stride % 128 == 0 && r.len + 33u >= 256u && r.out_stride < (1ull << 25);
+    else if constexpr (ST == ST_REGION)
+        staged = staged && 64 * r.out_stride <= REGION_MAX && ((64 * r.out_stride) >> 4) <= region_part16;
+    seal_fanout_wave<ST, PAIR>(payload, r.len, r.flags, subs + r.first_sub, subkeys, o, r.out_stride, r.count,
+                               fanout_owns(r.out_stride) ? 1 : 0, wv.first, staged, region_part16);
 }
 
 #if CZ_KPART_HAS(3)
@@ -3826,8 +3880,7 @@ hipError_t czk_seal_fanout(const void *payload, uint32_t len, uint32_t flags, co
     if (count == 0)
         return hipSuccess;
     dim3 grid((count + BLOCK - 1) / BLOCK);
-    const bool owns = (out_stride % 128 == 0 && out_stride < (1ull << 25)) ||
-                      (out_stride % 16 == 0 && 64 * out_stride <= REGION_MAX);
+    const bool owns = fanout_owns(out_stride);
     const bool al = ((((uintptr_t)payload | (uintptr_t)out | out_stride) & 15u) == 0);
     const int st = count >= 64u ? pick_staging(out_stride, len + 33u, al) : ST_DIRECT;
 #define CZ_FANOUT_LAUNCH(ST, PR, LDS)                                                                          \
@@ -3841,6 +3894,41 @@ hipError_t czk_seal_fanout(const void *payload, uint32_t len, uint32_t flags, co
     else
         CZ_FANOUT_LAUNCH(ST_DIRECT, true, 0);
 #undef CZ_FANOUT_LAUNCH
+    return hipGetLastError();
+}
+
+// The staging class cz_plan_fanout gives the full waves of a run (CZ_FANOUT_LINES / _REGION /
+// _DIRECT): czk_seal_fanout's choice for that run alone.  Host code, no device call.
+int czk_fanout_class(uint64_t out_stride, uint32_t len, uint32_t count, int aligned)
+{
+    const int st = count >= 64u ? pick_staging(out_stride, len + 33u, aligned != 0) : (int)ST_DIRECT;
+    return st == ST_LINES ? CZ_FANOUT_LINES : (st == ST_REGION ? CZ_FANOUT_REGION : CZ_FANOUT_DIRECT);
+}
+
+// Grouped PUB fan-out (k_seal_fanout_runs): the wave table holds class_count[CZ_FANOUT_LINES] waves
+// for the line emitter, then class_count[CZ_FANOUT_REGION] for the region emitter, then
+// class_count[CZ_FANOUT_DIRECT] lane-wise ones -- at most three launches whatever the number of
+// runs.  region_stride: the largest out_stride of the region slice (0 or above REGION_MAX / 64:
+// REGION_MAX / 64); every wave of that launch gets an LDS partition of 64 such slots.
+hipError_t czk_seal_fanout_runs(const cz_fanout_run *runs, const cz_fanout_wave *waves, const uint32_t class_count[3],
+                                uint32_t region_stride, const void *in, const cz_fanout_sub *subs,
+                                const void *subkeys, void *out, hipStream_t s)
+{
+    if (region_stride == 0 || region_stride > REGION_MAX / 64)
+        region_stride = REGION_MAX / 64;
+    const u32 part16 = (64u * ((region_stride + 15u) & ~15u)) >> 4;
+#define CZ_FANOUT_RUNS_LAUNCH(ST, PR, LDS, W0, NW)                                                             \
+    hipLaunchKernelGGL((k_seal_fanout_runs<ST, PR>), dim3(((NW) + WAVES - 1) / WAVES), dim3(BLOCK), (LDS), s, runs, \
+                       waves + (W0), (NW), (const uint8_t *)in, subs, (const uint8_t *)subkeys, (uint8_t *)out, part16)
+    const uint32_t nl = class_count[CZ_FANOUT_LINES], nr = class_count[CZ_FANOUT_REGION],
+                   nd = class_count[CZ_FANOUT_DIRECT];
+    if (nl)
+        CZ_FANOUT_RUNS_LAUNCH(ST_LINES, true, WAVES * (LINE_LDS_BYTES + HOLD_LDS_BYTES), 0, nl);
+    if (nr)
+        CZ_FANOUT_RUNS_LAUNCH(ST_REGION, false, (unsigned)(WAVES * 16u * part16), nl, nr);
+    if (nd)
+        CZ_FANOUT_RUNS_LAUNCH(ST_DIRECT, true, 0, nl + nr, nd);
+#undef CZ_FANOUT_RUNS_LAUNCH
     return hipGetLastError();
 }
 

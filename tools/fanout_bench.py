@@ -23,7 +23,13 @@ config's shape: N x the arena bytes and H2D), wall clock, legs interleaved; the 
 the fan-out routing forced on (cz_tune "fanout_min" = 64) and forced off (2^30); a pinned D2H copy of the
 same wire bytes is timed beside them as the floor a flush cannot go below.
 
-Writes one JSON (default profiles/fanout/fanout.json) and prints it."""
+--runs measures the grouped fan-out instead (cz_plan_fanout + cz_seal_fanout_runs: all the publishes of a
+flush group in one call), see runs_rows and engine_runs_leg: R runs x N subscribers x len on the device, and
+the 256 x publish flush with the frames in the segment plan, routed by fanout_min 64, and routed by
+fanout_short.
+
+Writes one JSON (default profiles/fanout/fanout.json, with --runs profiles/fanout/fanout_runs.json) and
+prints it."""
 import argparse
 import ctypes
 import json
@@ -164,6 +170,174 @@ def device_rows(args, torch, dev, batch, _lib, ab):
     return rows
 
 
+RUNS_R = (1, 16, 256)
+RUNS_N = (64, 1024)
+RUNS_LENS = (100, 256, 1024, 4096)
+
+
+def runs_rows(args, torch, dev, batch, _lib):
+    """--runs, device legs: R runs x N subscribers x len (R payloads, the same N keys for every run, counters
+    per (run, subscriber), slots of round_up(len + 33, 128)), same method as device_rows:
+      (d)   one cz_seal_fanout_runs call (at most three launches);
+      (axR) R cz_seal_fanout launches back to back (ctypes calls with prepared arguments);
+      (b')  the same R x N descriptors through cz_seal_segments at the segment length a flush of that size picks."""
+    L = _lib.lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    rows = []
+    for length in args.runs_lens:
+        for n in args.runs_n:
+            for nr in args.runs_r:
+                stride = round_up(length + 33, 128)
+                pstride = round_up(length, 16) + 16
+                payload = torch.empty(nr * pstride + 256, dtype=torch.uint8, device=dev)
+                batch.fill(payload, 1)
+                sub = torch.empty(n * 32, dtype=torch.uint8, device=dev)
+                batch.fill(sub, 3)
+                sub = sub.view(n, 32)
+                out = torch.empty(nr * n * stride, dtype=torch.uint8, device=dev)
+                rng = np.random.default_rng(nr * n + length)
+                subs = np.zeros(nr * n, dtype=batch.FANOUT_SUB_DTYPE)
+                subs["counter"] = rng.integers(0, 1 << 63, size=nr * n, dtype=np.uint64)
+                subs["key_idx"] = np.tile(np.arange(n), nr)
+                d_subs = torch.from_numpy(subs.view(np.uint8).copy()).to(dev)
+                runs = np.zeros(nr, dtype=batch.FANOUT_RUN_DTYPE)
+                runs["payload_off"] = np.arange(nr, dtype=np.uint64) * np.uint64(pstride)
+                runs["out_off"] = np.arange(nr, dtype=np.uint64) * np.uint64(n * stride)
+                runs["out_stride"], runs["len"], runs["count"] = stride, length, n
+                runs["first_sub"] = np.arange(nr) * n
+                t0 = time.perf_counter()
+                plan = batch.plan_fanout(runs, payload, out)
+                t_plan = time.perf_counter() - t0
+                plan.to(dev)
+                desc = np.zeros(nr * n, dtype=batch.DESC_DTYPE)
+                desc["in_off"] = np.repeat(runs["payload_off"], n)
+                desc["out_off"] = np.arange(nr * n, dtype=np.uint64) * np.uint64(stride)
+                desc["len"], desc["prev"] = length, -1
+                desc["key_idx"], desc["counter"] = subs["key_idx"], subs["counter"]
+                nblk = (length + 33 + 63) // 64
+                short = engine_seg_blocks(nr * n * nblk, nblk)
+                pl_short = batch.SegmentPlan(desc, seg_blocks=short).to(dev)
+                d_desc = torch.from_numpy(desc.view(np.uint8)).to(dev)
+                calls = [(n, length, payload.data_ptr() + r * pstride, 0, d_subs.data_ptr() + 16 * r * n, sub.data_ptr(),
+                          out.data_ptr() + r * n * stride, stride, stream) for r in range(nr)]
+                seal_one = L.cz_seal_fanout
+
+                def back_to_back():
+                    for a in calls:
+                        if seal_one(*a):
+                            raise RuntimeError(_lib.last_error())
+
+                # (prepared ctypes calls for (d) too: the Python wrapper's bounds checks cost more host time than
+                # the launch takes on the device, and the events would time the host)
+                seal_runs = L.cz_seal_fanout_runs
+                grouped_args = (plan.d_runs.data_ptr(), nr, plan.d_waves.data_ptr(),
+                                (ctypes.c_uint32 * 3)(*plan.class_count), plan.region_stride, payload.data_ptr(),
+                                d_subs.data_ptr(), sub.data_ptr(), out.data_ptr(), stream)
+
+                def grouped():
+                    if seal_runs(*grouped_args):
+                        raise RuntimeError(_lib.last_error())
+
+                batch.seal_fanout_runs(plan, payload, d_subs, sub, out)   # (the checked wrapper once: bounds)
+                legs = {"grouped": grouped,
+                        "fanout_x_r": back_to_back,
+                        "segments_short": lambda: batch.seal_segments(d_desc, pl_short, payload, out, sub)}
+                # sanity at the timed shape: the three legs write the same bodies
+                legs["segments_short"]()
+                want = out.clone()
+                for k in ("grouped", "fanout_x_r"):
+                    out.zero_()
+                    legs[k]()
+                    torch.cuda.synchronize()
+                    assert torch.equal(want.view(nr * n, stride)[:, :length + 33], out.view(nr * n, stride)[:, :length + 33]), \
+                        f"{k} and cz_seal_segments disagree"
+                del want
+                inner = {}
+                for k, fn in legs.items():     # warm-up, and enough calls for a ~2 ms window
+                    inner[k] = max(1, min(200, math.ceil(2.0 / max(event_ms(torch, fn, 1), 1e-3))))
+                times = {k: [] for k in legs}
+                for rep in range(args.reps):
+                    for k, fn in legs.items():
+                        times[k].append(event_ms(torch, fn, inner[k]))
+                row = {"runs": nr, "n": n, "lanes": nr * n, "len": length, "out_stride": stride, "waves": plan.nwaves,
+                       "class_count": plan.class_count, "plan_host_ms": round(t_plan * 1e3, 4),
+                       "grouped_metadata_bytes": int(runs.nbytes + plan.waves.nbytes + subs.nbytes),
+                       "short_seg_blocks": short, "short_segments": pl_short.nseg}
+                for k in legs:
+                    med = statistics.median(times[k])
+                    row[k + "_ms"] = round(med, 5)
+                    row[k + "_all_ms"] = [round(t, 5) for t in times[k]]
+                    row[k + "_calls_per_window"] = inner[k]
+                rows.append(row)
+                print(f"R={nr} n={n} len={length}: " + ", ".join(f"{k} {row[k + '_ms']} ms" for k in legs), file=sys.stderr)
+                del payload, sub, out, d_subs, d_desc, pl_short, plan
+                torch.cuda.empty_cache()
+    return rows
+
+
+def engine_runs_leg(args, _lib, length):
+    """--runs, engine leg: --engine-msgs x publish of `length` bytes to --engine-conns connections, flushed with
+    the frames left in the segment plan, with fanout_min 64, and with fanout_short = length (fanout_min at its
+    default); wall clock of flush_out, one warm-up round, legs interleaved."""
+    from jeromq_amd.engine import CurveBatchEngine
+    L = _lib.lib()
+    nc, nm = args.engine_conns, args.engine_msgs
+    body = length + 33
+    wire_bytes = nc * nm * (body + (9 if body > 255 else 2))
+    payloads = [np.random.default_rng(m).integers(0, 256, size=length, dtype=np.uint8).tobytes() for m in range(nm)]
+    eng = CurveBatchEngine(arena_bytes=nm * round_up(length, 16) + 4096)
+    cc = [eng.add_connection(np.random.default_rng(1000 + i).integers(0, 256, size=32, dtype=np.uint8).tobytes())
+          for i in range(nc)]
+    ids = (ctypes.c_int * nc)(*cc)
+    default_min = L.cz_tune(b"fanout_min", 1 << 30)
+    L.cz_tune(b"fanout_min", default_min)
+    routings = {"segments": (1 << 30, 0), "fanout_min_64": (64, 0), "fanout_short": (default_min, length)}
+
+    def run(fmin, fshort):
+        old = L.cz_tune(b"fanout_min", fmin), L.cz_tune(b"fanout_short", fshort)
+        try:
+            for p in payloads:
+                _lib.check(L.cz_engine_publish(eng._h, ids, nc, p, length, 0, None), "cz_engine_publish")
+            t0 = time.perf_counter()
+            eng.flush_out()
+            return time.perf_counter() - t0
+        finally:
+            L.cz_tune(b"fanout_min", old[0])
+            L.cz_tune(b"fanout_short", old[1])
+
+    res = {k: [] for k in routings}
+    for rep in range(args.reps + 1):
+        for k, (fmin, fshort) in routings.items():
+            t = run(fmin, fshort)
+            if rep:
+                res[k].append(t)
+    eng.close()
+    out = {"connections": nc, "messages": nm, "len": length, "wire_bytes": wire_bytes, "clock": "time.perf_counter"}
+    for k, v in res.items():
+        out[k + "_flush_ms"] = round(statistics.median(v) * 1e3, 3)
+        out[k + "_flush_all_ms"] = [round(t * 1e3, 3) for t in v]
+    return out
+
+
+def fanout_short_rule(rows, engines):
+    """The rule that sets the shipped fanout_short: the largest measured length at which the grouped call is not
+    slower than (b') in the median at every measured R x N >= 1024 and the engine flush routed by fanout_short is
+    not slower than the segment-plan flush of the same run -- and every shorter measured length qualifies too
+    (the knob routes everything up to its value); 0 if none."""
+    verdict = {}
+    for length in sorted({r["len"] for r in rows}):
+        dev_ok = all(r["grouped_ms"] <= r["segments_short_ms"] for r in rows if r["len"] == length and r["lanes"] >= 1024)
+        eng = [e for e in engines if e["len"] == length]
+        eng_ok = bool(eng) and all(e["fanout_short_flush_ms"] <= e["segments_flush_ms"] for e in eng)
+        verdict[str(length)] = {"device": dev_ok, "engine": eng_ok if eng else None}
+    best = 0
+    for length in sorted(int(k) for k in verdict):
+        if not (verdict[str(length)]["device"] and verdict[str(length)]["engine"]):
+            break
+        best = length
+    return verdict, best
+
+
 def engine_leg(args, torch, _lib):
     from jeromq_amd.engine import CurveBatchEngine
     L = _lib.lib()
@@ -252,8 +426,15 @@ def main():
     ap.add_argument("--engine-len", type=int, default=4096)
     ap.add_argument("--no-engine", action="store_true")
     ap.add_argument("--no-device", action="store_true", help="skip the device legs")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fanout", "fanout.json"))
+    ap.add_argument("--runs", action="store_true",
+                    help="the grouped fan-out instead: R runs x N subscribers (default --out: fanout_runs.json)")
+    ap.add_argument("--runs-r", type=int, nargs="*", default=list(RUNS_R))
+    ap.add_argument("--runs-n", type=int, nargs="*", default=list(RUNS_N))
+    ap.add_argument("--runs-lens", type=int, nargs="*", default=list(RUNS_LENS))
+    ap.add_argument("--engine-runs-lens", type=int, nargs="*", default=list(RUNS_LENS))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "fanout", "fanout_runs.json" if args.runs else "fanout.json")
     if args.reps < 5:
         ap.error("--reps must be at least 5")
     import torch
@@ -268,9 +449,20 @@ def main():
     out = {"device": torch.cuda.get_device_name(0), "library": _lib.lib().cz_version().decode(),
            "fanout_kernels_sha256": build.kernel_code_sha256(_lib.LIB_PATH, kernels), "reps": args.reps,
            "clock_device": "hipEvent (torch.cuda.Event), median", "ab_lib": args.ab_name or args.ab_lib}
-    if not args.no_device:
+    if args.runs:
+        out["fanout_runs_kernels_sha256"] = build.kernel_code_sha256(
+            _lib.LIB_PATH, [k.replace("k_seal_fanout<", "k_seal_fanout_runs<") for k in kernels])
+        out["fanout_short_default"] = _lib.lib().cz_tune(b"fanout_short", 0)
+        _lib.lib().cz_tune(b"fanout_short", out["fanout_short_default"])
+        if not args.no_device:
+            out["runs_legs"] = runs_rows(args, torch, dev, batch, _lib)
+        if not args.no_engine:
+            out["engine_runs"] = [engine_runs_leg(args, _lib, length) for length in args.engine_runs_lens]
+        if "runs_legs" in out and "engine_runs" in out:
+            out["fanout_short_verdict"], out["fanout_short_rule"] = fanout_short_rule(out["runs_legs"], out["engine_runs"])
+    elif not args.no_device:
         out["device_legs"] = device_rows(args, torch, dev, batch, _lib, ab)
-    if not args.no_engine:
+    if not args.no_engine and not args.runs:
         out["engine"] = engine_leg(args, torch, _lib)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
