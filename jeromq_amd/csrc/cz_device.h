@@ -292,6 +292,13 @@ __device__ __forceinline__ u64 mad64(u32 a, u32 b, u64 c) { return (u64)a * b + 
 // h = (h + m + hibit*2^128) * r  (partially reduced).  Written as explicit 32-bit
 // carry chains (v_add_co_u32 / v_addc_co_u32) around 19 v_mad_u64_u32: the plain
 // u64 formulation compiled to zero-extension moves and 64-bit adds.
+// CIN (the seal pair loop): the fold's carry chain as five instructions of one asm statement, its
+// last carry entering h4 as the carry-in of a v_addc_co_u32.  Left to the compiler, h4's carry is
+// selected into a register (v_cndmask_b32 0, 1) and added: one VALU more per block.  The compiler
+// inserts no wait states inside an asm statement: gfx950 needs two between a VALU write of VCC and
+// a VALU read of it as carry-in, hence the s_nop 1 before each v_addc_co_u32.  All operands are
+// VGPRs and each output is tied to the input it replaces.
+template <bool CIN = false>
 __device__ __forceinline__ void poly_block(Poly &P, u32 m0, u32 m1, u32 m2, u32 m3, u32 hibit)
 {
     u32 c;
@@ -321,11 +328,24 @@ __device__ __forceinline__ void poly_block(Poly &P, u32 m0, u32 m1, u32 m2, u32 
     // k = 5q as one v_lshl_add_u32: left to itself the compiler emits (x & ~3) + q, two VALU
     u32 k;
     asm("v_lshl_add_u32 %0, %1, 2, %1" : "=v"(k) : "v"(q));
-    P.h0 = addc((u32)d0, k, 0u, c);
-    P.h1 = addc((u32)d1, (u32)(d0 >> 32), c, c);
-    P.h2 = addc((u32)d2, (u32)(d1 >> 32), c, c);
-    P.h3 = addc((u32)d3, (u32)(d2 >> 32), c, c);
-    P.h4 = (x & 3u) + c;
+    if constexpr (CIN) {
+        u32 a0 = (u32)d0, a1 = (u32)d1, a2 = (u32)d2, a3 = (u32)d3, a4 = x & 3u;
+        asm("v_add_co_u32 %0, vcc, %0, %5\n\ts_nop 1\n\t"
+            "v_addc_co_u32 %1, vcc, %1, %6, vcc\n\ts_nop 1\n\t"
+            "v_addc_co_u32 %2, vcc, %2, %7, vcc\n\ts_nop 1\n\t"
+            "v_addc_co_u32 %3, vcc, %3, %8, vcc\n\ts_nop 1\n\t"
+            "v_addc_co_u32 %4, vcc, 0, %4, vcc"
+            : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4)
+            : "v"(k), "v"((u32)(d0 >> 32)), "v"((u32)(d1 >> 32)), "v"((u32)(d2 >> 32))
+            : "vcc");
+        P.h0 = a0; P.h1 = a1; P.h2 = a2; P.h3 = a3; P.h4 = a4;
+    } else {
+        P.h0 = addc((u32)d0, k, 0u, c);
+        P.h1 = addc((u32)d1, (u32)(d0 >> 32), c, c);
+        P.h2 = addc((u32)d2, (u32)(d1 >> 32), c, c);
+        P.h3 = addc((u32)d3, (u32)(d2 >> 32), c, c);
+        P.h4 = (x & 3u) + c;
+    }
 }
 
 // Final block of len bytes (1..15): bytes >= len cleared, byte len = 0x01, no 2^128 bit.

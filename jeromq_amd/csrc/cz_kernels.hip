@@ -668,21 +668,25 @@ __device__ __forceinline__ void seal_frame(const uint8_t *__restrict__ in0, u32 
 
     // ZMQ, one full block b >= 1 from its 17-dword window W = P[16b-9 .. 16b+7]; STEADY: a block of
     // the pair loop (b >= 2), emitted through the emitter's steady-state form if it has one
-    auto zmq_block = [&](u32 blk, const u32 *W, auto steady) {
+    // (win(q) = dword q of the window: the pair loop reads it from two lines' registers in place)
+    auto zmq_block_win = [&](u32 blk, auto win, auto steady) {
         ksblock(x, blk, 0u);
 #pragma unroll
         for (int k = 0; k < 16; k++)
-            C[k] = funnel(W[k + 1], W[k], sh) ^ x[k];
-        poly_block(P, C[0], C[1], C[2], C[3], 1u);
-        poly_block(P, C[4], C[5], C[6], C[7], 1u);
-        poly_block(P, C[8], C[9], C[10], C[11], 1u);
-        poly_block(P, C[12], C[13], C[14], C[15], 1u);
-        if constexpr (decltype(steady)::value)
+            C[k] = funnel(win(k + 1), win(k), sh) ^ x[k];
+        constexpr bool STEADY = decltype(steady)::value;  // the pair loop: Poly1305's fold with h4 as carry-in
+        poly_block<STEADY>(P, C[0], C[1], C[2], C[3], 1u);
+        poly_block<STEADY>(P, C[4], C[5], C[6], C[7], 1u);
+        poly_block<STEADY>(P, C[8], C[9], C[10], C[11], 1u);
+        poly_block<STEADY>(P, C[12], C[13], C[14], C[15], 1u);
+        if constexpr (STEADY)
             emit_steady(em, blk, C);
         else
             em.emit_full(blk, C);
     };
-    auto zmq_full_block = [&](u32 blk, const u32 *W) { zmq_block(blk, W, std::false_type{}); };
+    auto zmq_full_block = [&](u32 blk, const u32 *W) {
+        zmq_block_win(blk, [&](int q) { return W[q]; }, std::false_type{});
+    };
 
     // box-aligned input, one full block b >= 1 from its 16 dwords
     [[maybe_unused]] auto box_full_block = [&](u32 blk, const u32 *W) {
@@ -786,49 +790,53 @@ __device__ __forceinline__ void seal_frame(const uint8_t *__restrict__ in0, u32 
         }
         carry = L[7];
         if (nfull >= 2) {
-            // Chunks 6 and 7 of a line (bytes 96..127) matter only as the carry of the next
-            // iteration; past the payload end they are not loaded and the registers keep stale,
-            // unused words (no zero fill: -8 v_mov per pair).  (Loading line k + 1 at the end of
-            // iteration k, ahead of the line stores, measured 2% slower.)
-            auto load_line = [&](u32 k) {
+            // Line k serves blocks 2k and 2k+1: block 2k's window is dwords 23..31 of line k-1 (kept
+            // in L) and dwords 0..7 of line k (loaded into M), block 2k+1's is dwords 7..23 of line k.
+            // (Loading line k + 1 at the end of iteration k, ahead of the line stores, measured 2%
+            // slower; two iterations per trip over swapped register sets, which needs no copy of a
+            // line's end, measured 0.6% slower than this loop at 1908 instead of 1920 VALU per pair:
+            // 29 KiB of loop.  DESIGN.md section 6.)
+            auto load_chunks = [&](u32 k, u32 *D, auto nch) {
                 const uint8_t *src = in + 128u * k;
-                const u32 o = 128u * k;
 #pragma unroll
-                for (int c = 0; c < 6; c++) {
+                for (int c = 0; c < decltype(nch)::value; c++) {
                     V4 v = ldF(src + 16 * c);
-                    L[4 * c] = v.x; L[4 * c + 1] = v.y; L[4 * c + 2] = v.z; L[4 * c + 3] = v.w;
-                }
-#pragma unroll
-                for (int c = 6; c < 8; c++) {
-                    if (inlen > o + 16u * c) {
-                        V4 v = INA == 16 ? ld16f_in<AL>(src + 16 * c) : ldP(src + 16 * c, inlen - o - 16u * c);
-                        L[4 * c] = v.x; L[4 * c + 1] = v.y; L[4 * c + 2] = v.z; L[4 * c + 3] = v.w;
-                    }
+                    D[4 * c] = v.x; D[4 * c + 1] = v.y; D[4 * c + 2] = v.z; D[4 * c + 3] = v.w;
                 }
             };
-            u32 cy[9];
+            auto pair = [&](u32 k, const u32 *Cur, const u32 *Prev) {
+                zmq_block_win(2u * k, [&](int q) { return q < 9 ? Prev[23 + q] : Cur[q - 9]; }, std::true_type{});
+                zmq_block_win(2u * k + 1u, [&](int q) { return Cur[7 + q]; }, std::true_type{});
+            };
             zmq_full_block(1, L + 7);
+            // Steady iterations: the whole 128-byte line lies inside the payload, all 8 loads
+            // unconditional.  Every pair iteration but the last is steady (line k ends at payload
+            // byte 128k + 128 <= n + 33 whenever block 2k + 1 is full), the last one when the
+            // payload covers its line too (a 4096-byte payload: all 31).
+            const u32 kend = nfull >> 1;  // pair iterations: 2k + 1 < nfull
+            // (INA 1: inlen = n - d is per-lane; n - 3 bounds it from below and keeps the trip counts,
+            // and with them the block counter, wave-uniform where n is)
+            const u32 klines = INA == 1 ? (n > 3u ? (n - 3u) >> 7 : 0u) : (u32)(inlen >> 7);
+            const u32 kst = kend < klines ? kend : klines;
+            u32 M[32];
+            u32 k = 1;
+            for (; k < kst; k++) {
+                load_chunks(k, M, std::integral_constant<int, 8>{});
+                pair(k, M, L);
 #pragma unroll
-            for (int q = 0; q < 9; q++)
-                cy[q] = L[23 + q];
-            blk = 2;
-            for (u32 k = 1; 2u * k + 1u < nfull; k++) {
-                load_line(k);
-                u32 W[17];
-#pragma unroll
-                for (int q = 0; q < 9; q++)
-                    W[q] = cy[q];
-#pragma unroll
-                for (int q = 0; q < 8; q++)
-                    W[9 + q] = L[q];
-                zmq_block(2u * k, W, std::true_type{});
-                zmq_block(2u * k + 1u, L + 7, std::true_type{});
-#pragma unroll
-                for (int q = 0; q < 9; q++)
-                    cy[q] = L[23 + q];
-                blk = 2u * k + 2u;
+                for (int q = 23; q < 32; q++)
+                    L[q] = M[q];
             }
-            carry = cy[0];  // P[16*blk - 9] for the per-block path below
+            // A last iteration whose line the payload does not cover: its bytes 96..127 would only
+            // be the carry of an iteration that does not follow, and are not loaded.
+            if (k < kend) {
+                load_chunks(k, M, std::integral_constant<int, 6>{});
+                pair(k, M, L);
+                L[23] = M[23];
+                k++;
+            }
+            blk = 2u * k;
+            carry = L[23];  // P[16*blk - 9] for the per-block path below
         } else {
             blk = nfull > 1 ? nfull : 1u;
         }
