@@ -146,11 +146,17 @@ int cz_open_batch(const cz_frame_desc *d_desc, const uint32_t *d_order, uint32_t
 /* Uniform-length batch of ONE connection direction: frame i at in + i*in_stride,
  * body i at out + i*out_stride, nonce counter0 + i, flags d_flags8[i] (NULL = 0).
  * Any strides and base alignments: payloads packed at any byte offset are read with
- * dword-aligned loads; an out_stride that is a multiple of 128 (or 64 slots <= 16 KiB)
- * makes the batch own count * out_stride output bytes, and slot bytes past a body are
- * written as zero (whole 128-byte lines stored once); any other out_stride (e.g. bodies
- * back to back, 4129 bytes apart at 4 KiB) goes through byte-shifted line staging and
- * leaves the bytes between bodies as the caller wrote them. */
+ * dword-aligned loads.
+ * OUTPUT OWNERSHIP, decided by out_stride alone (the same rule as section 3c): with an
+ * out_stride that is a multiple of 128 below 32 MiB (2^25), or a multiple of 16 of at most
+ * 256 (64 slots in 16 KiB), the batch owns count * out_stride output bytes and every slot
+ * byte past a body is written as zero, whatever the length, the count and the base
+ * alignments (full waves of 16-byte aligned slots store whole 128-byte lines once; other
+ * layouts and the last partial wave store lane by lane and zero the rest of the slot
+ * themselves).  With any other out_stride -- e.g. bodies back to back, 4129 bytes apart
+ * at 4 KiB, or slots of 32 MiB and more -- only the count bodies are written and the bytes
+ * between them stay as the caller wrote them (below 4 MiB through byte-shifted line
+ * staging, lane by lane above). */
 int cz_seal_uniform(uint32_t count, uint32_t len, const void *d_in, uint64_t in_stride, void *d_out,
                     uint64_t out_stride, const void *d_subkey, uint64_t counter0, const uint8_t *d_flags8,
                     void *stream);
@@ -164,9 +170,10 @@ int cz_seal_uniform_box(uint32_t count, uint32_t len, const void *d_box, uint64_
 /* Open `count` bodies of `size` bytes of one connection in order; frame 0 must
  * beat floor0, frame i must beat frame i-1 (when check != 0).  Payload i goes to
  * out + i*out_stride.  Bodies at any byte offset (in_stride 4129: the dense wire
- * layout) are read with dword-aligned loads.  out_stride a multiple of 128: the batch
- * owns count * out_stride output bytes (slot bytes past a payload, and rejected frames'
- * slots, are written as zero); any other out_stride: byte-shifted line staging, bytes
+ * layout) are read with dword-aligned loads.  Output ownership by out_stride alone, the
+ * rule of cz_seal_uniform: a multiple of 128 below 32 MiB, or a multiple of 16 of at most
+ * 256 -- the batch owns count * out_stride output bytes (slot bytes past a payload, and
+ * rejected frames' whole slots, are written as zero); any other out_stride -- bytes
  * between payloads untouched, rejected frames' payload bytes written as zero. */
 int cz_open_uniform(uint32_t count, uint32_t size, const void *d_in, uint64_t in_stride, void *d_out,
                     uint64_t out_stride, const void *d_subkey, uint64_t floor0, int check, uint16_t *d_status,

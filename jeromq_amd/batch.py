@@ -42,8 +42,10 @@ def subkeys(precom, direction, stream=None):
 
 def seal_uniform(inp, in_stride, out, out_stride, count, length, subkey, counter0, flags8=None, stream=None):
     """Seal `count` payloads of `length` bytes (frame i at in[i*in_stride]) into MESSAGE
-    bodies; body i goes to slot i = out[i*out_stride : (i+1)*out_stride].  The batch owns
-    whole slots: slot bytes past the body are written (as zeros)."""
+    bodies; body i goes to slot i = out[i*out_stride : (i+1)*out_stride].  With an out_stride
+    that is a multiple of 128 below 2^25, or a multiple of 16 up to 256, the batch owns whole
+    slots: slot bytes past the body are written as zeros; with any other stride they are left
+    as they were (cz_seal_uniform in include/curvezmq_mi355x.h)."""
     _need_cuda_u8(inp, "in")
     _need_cuda_u8(out, "out")
     need_in = (count - 1) * in_stride + length if count else 0

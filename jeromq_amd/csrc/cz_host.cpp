@@ -34,6 +34,7 @@ hipError_t czk_open_uniform(const void *, uint64_t, void *, uint64_t, uint32_t, 
 hipError_t czk_fill(void *, uint64_t, uint64_t, hipStream_t);
 hipError_t czk_copy16(void *, const void *, uint64_t, hipStream_t);
 int czk_tune(const char *, int);
+int czk_owns_slots(uint64_t);
 }
 
 namespace czi {
@@ -1186,9 +1187,9 @@ static int ctx_uniform(cz_ctx *c, bool seal, uint32_t count, uint32_t len, const
                             (reuse && (e = hipStreamWaitEvent(s_k, c->ev_out[q], 0)) != hipSuccess)))
             return hip_fail(e, "event");
         if (seal) {
-            // a slot stride off the 128-byte lines leaves the bytes between bodies to the caller
+            // a stride that does not own its slots leaves the bytes between bodies to the caller
             // (cz_seal_uniform): zero them, so the host gets whole slots on every path
-            e = out_stride % 128 ? hipMemsetAsync(c->pout[q].ptr, 0, (uint64_t)nc * out_stride, s_k) : hipSuccess;
+            e = czk_owns_slots(out_stride) ? hipSuccess : hipMemsetAsync(c->pout[q].ptr, 0, (uint64_t)nc * out_stride, s_k);
             if (e == hipSuccess)
                 e = czk_seal_uniform(c->pin[q].ptr, in_stride, c->pout[q].ptr, out_stride, nc, len, c->subkeys.ptr,
                                      counter0 + f0, dfl, s_k);

@@ -2773,11 +2773,54 @@ __global__ __launch_bounds__(BLOCK) CZ_OCC CZ_OPEN_UNI_OCC void k_seal_fanout(
                                (blockIdx.x * BLOCK + threadIdx.x) & ~63u, true, (64u * (u32)out_stride) >> 4);
 }
 
-// The output-ownership rule of a fan-out run (header section 3c), by its stride alone.
+// The output-ownership rule of a uniform batch and of a fan-out run (header sections 3 and 3c), by
+// the stride alone: whichever emitter the alignments and the length select, the slots of such a
+// batch are written whole.  (2^25: EmitLines' 32-bit offsets; a larger slot is not worth zeroing.)
 __host__ __device__ __forceinline__ bool fanout_owns(uint64_t out_stride)
 {
     return (out_stride % 128 == 0 && out_stride < (1ull << 25)) || (out_stride % 16 == 0 && 64 * out_stride <= REGION_MAX);
 }
+
+#if CZ_KPART_HAS(1) || CZ_KPART_HAS(2)
+// Zero bytes [from, stride) of `count` output slots: what a uniform batch that owns its slots owes
+// past the bytes its seal / open kernel wrote.  The uniform kernels write zeros only where their
+// emitter does anyway (EmitLines to the end of the last line, EmitRegion the whole slot, the partial
+// last wave of those two the rest of its slots); a longer slot, a line-multiple stride with a body too
+// short for the line emitter, or a base off 16-byte alignment left the rest of an owned slot as the
+// caller wrote it.  A launch of its own, made only for such a layout, keeps the seal and open kernels
+// as they are (a tail in the kernels put selects into the headline's pair loop).  One 4 KiB chunk per
+// workgroup trip, 16 bytes per lane, any byte alignment.
+__global__ __launch_bounds__(BLOCK) void k_zero_pad(uint8_t *__restrict__ out, uint64_t stride, uint32_t count,
+                                                    uint32_t from)
+{
+    static_assert(BLOCK * 16 == 4096, "one chunk per workgroup trip");
+    const uint64_t pad = stride - from;
+    const uint64_t per = (pad + 4095u) / 4096u;  // chunks per slot
+    const uint64_t total = per * count;
+    for (uint64_t c = blockIdx.x; c < total; c += gridDim.x) {
+        const uint64_t i = c / per, o = (c % per) * 4096u + 16u * threadIdx.x;
+        if (o >= pad)
+            continue;
+        uint8_t *p = out + i * stride + from + o;
+        const uint64_t nb = pad - o;
+        if (nb >= 16u)
+            reinterpret_cast<U16ua *>(p)->v = make_uint4(0u, 0u, 0u, 0u);
+        else  // the last slot bytes, fewer than 16
+            for (u32 b = 0; b < (u32)nb; b++)
+                p[b] = 0;
+    }
+}
+
+// after a uniform kernel that wrote bytes [0, done) of every slot (and whatever zeros its emitter adds)
+static void zero_pad_launch(void *out, uint64_t stride, uint32_t count, uint32_t done, hipStream_t s)
+{
+    if (count == 0 || stride <= done || !fanout_owns(stride))
+        return;
+    const uint64_t total = ((stride - done + 4095u) / 4096u) * count;
+    hipLaunchKernelGGL(k_zero_pad, dim3((unsigned)(total < (1u << 18) ? total : (1u << 18))), dim3(BLOCK), 0, s,
+                       (uint8_t *)out, stride, count, done);
+}
+#endif
 
 // Every fan-out run of a flush group in one launch per staging class (cz_seal_fanout_runs): wave w
 // of this launch's slice of the wave table serves subscribers [first, first + 64) of run
@@ -3818,11 +3861,13 @@ hipError_t czk_seal_uniform(const void *in, uint64_t in_stride, void *out, uint6
         if (so == ST_LINES) {
             if (i8) CZ_SEAL_LAUNCH_INA(ST_LINES, true, 8, lds_l);
             else CZ_SEAL_LAUNCH_INA(ST_LINES, true, 1, lds_l);
+            zero_pad_launch(out, out_stride, count, (len + 33u + 127u) & ~127u, s);
             return hipGetLastError();
         }
         if (so == ST_SHIFT) {
             if (i8) CZ_SEAL_LAUNCH_INA(ST_SHIFT, true, 8, lds_s);
             else CZ_SEAL_LAUNCH_INA(ST_SHIFT, true, 1, lds_s);
+            zero_pad_launch(out, out_stride, count, len + 33u, s);
             return hipGetLastError();
         }
         if (so == ST_REGION) {
@@ -3853,8 +3898,16 @@ hipError_t czk_seal_uniform(const void *in, uint64_t in_stride, void *out, uint6
         else CZ_SEAL_LAUNCH(ST_DIRECT, false, 0);
     }
 #undef CZ_SEAL_LAUNCH
+    // the rest of owned slots (header section 3): nothing for the region emitter, which writes whole
+    // slots, nor for line-staged slots that end with the body's last line
+    if (st != ST_REGION)
+        zero_pad_launch(out, out_stride, count, st == ST_LINES ? (len + 33u + 127u) & ~127u : len + 33u, s);
     return hipGetLastError();
 }
+
+// 1 when a uniform batch with this out_stride owns its whole slots (the host-staged paths zero the
+// slots themselves when it does not).  Host code, no device call.
+int czk_owns_slots(uint64_t out_stride) { return fanout_owns(out_stride) ? 1 : 0; }
 
 // Box-layout input (MODE_BOX): whole-line staging for 128-byte multiple output slots, direct
 // stores otherwise; whole-line input loads always (the box is read where it lies).
@@ -3874,6 +3927,7 @@ hipError_t czk_seal_uniform_box(const void *in, uint64_t in_stride, void *out, u
         hipLaunchKernelGGL((k_seal_uniform<ST_DIRECT, true, MODE_BOX>), grid, dim3(BLOCK), 0, s, (const uint8_t *)in,
                            in_stride, (uint8_t *)out, out_stride, count, len, (const uint8_t *)subkey, counter0, nullptr,
                            g_un0);
+    zero_pad_launch(out, out_stride, count, st == ST_LINES ? (len + 33u + 127u) & ~127u : len + 33u, s);
     return hipGetLastError();
 }
 
@@ -4048,6 +4102,7 @@ hipError_t czk_open_uniform(const void *in, uint64_t in_stride, void *out, uint6
                 hipLaunchKernelGGL((k_open_uniform_carry<1>), cgrid, dim3(BLOCK), WAVES * LINE_LDS_BYTES, s,
                                    (const uint8_t *)in, in_stride, (uint8_t *)out, out_stride, nwaves, P, size,
                                    (const uint8_t *)subkey, floor0, check, status, g_un0);
+            zero_pad_launch(out, out_stride, count, (nout + 127u) & ~127u, s);
             const uint64_t done = blocks * 64ull * P;
             if (done < count) {
                 hipError_t e = hipGetLastError();
@@ -4082,6 +4137,7 @@ hipError_t czk_open_uniform(const void *in, uint64_t in_stride, void *out, uint6
         } else {
             CZ_OPEN_LAUNCH_INA(ST_SHIFT, 1, WAVES * SHIFT_LDS_BYTES);
         }
+        zero_pad_launch(out, out_stride, count, st_out == ST_LINES ? (nout + 127u) & ~127u : nout, s);
         return hipGetLastError();
     }
     if (g_pair && st != ST_REGION) {
@@ -4092,6 +4148,9 @@ hipError_t czk_open_uniform(const void *in, uint64_t in_stride, void *out, uint6
         else if (st == ST_REGION) CZ_OPEN_LAUNCH(ST_REGION, false, lds);
         else CZ_OPEN_LAUNCH(ST_DIRECT, false, 0);
     }
+    // the rest of owned slots, as czk_seal_uniform
+    if (st != ST_REGION)
+        zero_pad_launch(out, out_stride, count, st == ST_LINES ? (nout + 127u) & ~127u : nout, s);
 #undef CZ_OPEN_LAUNCH
 #undef CZ_OPEN_LAUNCH_INA
     return hipGetLastError();

@@ -381,6 +381,8 @@ def test_jni_seal_open_through_the_shim(shim):
         pytest.skip("no GPU")
     L = shim
     L.fake_set_copy_mode(1)
+    L.fake_reset_log()          # (the pin detector's own check in an earlier test leaves its count behind)
+    L.fake_reset_lib_calls()
     try:
         payload = splitmix_bytes(100, 11)
         m = np.zeros(133, dtype=np.uint8)
