@@ -674,6 +674,48 @@ int cz_connector_release(cz_connector *c, int32_t slot);
 /* slots in use (handed out by stage 1 and not yet released) */
 uint32_t cz_connector_pending(const cz_connector *c);
 
+/* ---- 13. bulk session hand-over: N finished handshakes into the engine at once (with section 8) ----
+ * The last step of a reconnect storm.  The reference attaches one connection at a time: each
+ * StreamEngine takes its own mechanism to READY (StreamEngine.java nextHandshakeCommand :886-912,
+ * processHandshakeCommand :914-935, mechanismReady :958) and tears it down alone (unplug / error, :334-370, :1116-1131).  Sections
+ * 11 and 12 finish N handshakes in a fixed number of launches; these calls move the N sessions into
+ * the engine, and out of it and of the handshake's slot table, in a fixed number as well: one subkey
+ * table growth at most, one k_session_subkeys launch (one lane per session and direction), one wipe of
+ * the staging and one synchronisation, whatever N is.
+ * The add calls are drop-in for the loop of single adds: ids[i] is the id (and the subkey slots are those)
+ * that the i-th single call would have returned on the same engine -- ids freed by cz_engine_remove_conn
+ * first, last freed first, then new ids in order -- and a slot named twice gives two connections.
+ * Per item: a slot that is out of range or holds no completed handshake gives ids[i] = CZ_EINVAL,
+ * consumes no id, and the other items proceed (the call returns CZ_OK).  For the call: CZ_EINVAL (null
+ * pointers) or CZ_EHIP (any HIP error) leave the engine exactly as it was, with every ids[i] negative.
+ * count == 0 returns CZ_OK and launches nothing. */
+/* cz_engine_add_conn (the mechanism constructors, CurveClientMechanism.java:55-78 /
+ * CurveServerMechanism.java:55-75, with the state of a finished handshake) for count sessions from host
+ * keys.  as_server: count flags, NULL = all clients; precoms: count x 32 bytes, staged through pinned
+ * memory in one copy and wiped there and on the device before the call returns. */
+int cz_engine_add_conns(cz_engine *e, uint32_t count, const uint8_t *as_server, const uint8_t *precoms,
+                        const uint64_t *cn_nonce, const uint64_t *cn_peer_nonce, int32_t *ids);
+/* cz_engine_add_accepted / cz_engine_add_connected for count slots: cnPrecom is read from the
+ * handshake's device state, where it lies until the slot is released, and does not pass through the
+ * host (a handshake on another device than the engine: its host copy is staged as above).  Nonces as the
+ * single calls set them.  The call returns after the engine's synchronisation, so the slots may be
+ * released at once. */
+int cz_engine_add_accepted_batch(cz_engine *e, const cz_acceptor *a, uint32_t count, const int32_t *slots,
+                                 int32_t *ids);
+int cz_engine_add_connected_batch(cz_engine *e, const cz_connector *c, uint32_t count, const int32_t *slots,
+                                  int32_t *ids);
+/* cz_engine_remove_conn (StreamEngine unplug / error, StreamEngine.java:334-370,1116-1131) for a list:
+ * rcs[i] = what the i-th single call would return (CZ_EINVAL for an id that is unknown, already
+ * removed or named before in the list; the others proceed), the ids are reused in the order the loop
+ * would leave them, and the subkeys are wiped by one launch with one synchronisation. */
+int cz_engine_remove_conns(cz_engine *e, uint32_t count, const int *conns, int32_t *rcs);
+/* cz_acceptor_release / cz_connector_release (the mechanism's destroy(), Mechanism.java:379) for a list,
+ * all or nothing: every slot must be in use and none named twice, else CZ_EINVAL with nothing
+ * released; the device records are wiped by one launch on the handshake's stream and the slots freed
+ * in list order. */
+int cz_acceptor_release_batch(cz_acceptor *a, uint32_t count, const int32_t *slots);
+int cz_connector_release_batch(cz_connector *c, uint32_t count, const int32_t *slots);
+
 /* ---- 6. misc -------------------------------------------------------------- */
 const char *cz_last_error(void);
 const char *cz_version(void);

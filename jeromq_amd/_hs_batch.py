@@ -92,5 +92,11 @@ class _HsBatch:
     def release(self, slot):
         self._call("release", self._h, slot)
 
+    def release_many(self, slots):
+        """release() for a list, all or nothing: one device launch wipes every slot's record.  A slot
+        that is not in use or is named twice raises with nothing released."""
+        arr = np.array(list(slots), dtype=np.int32)
+        self._call("release_batch", self._h, len(arr), arr.ctypes.data_as(ctypes.c_void_p))
+
     def pending(self):
         return int(getattr(self._L, self._prefix + "_pending")(self._h))

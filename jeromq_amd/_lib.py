@@ -223,7 +223,13 @@ SIGNATURES = {
     "cz_engine_add_connected": (_I, [_VP, _VP, ctypes.c_int32]),
     "cz_connector_release": (_I, [_VP, ctypes.c_int32]),
     "cz_connector_pending": (_U32, [_VP]),
-    "cz_zmtp_metadata_check": (_I, [_VP, _U64, _I]),
+    "cz_engine_add_conns": (_I, [_VP, _U32, _VP, _VP, _VP, _VP, _VP]),
+    "cz_engine_add_accepted_batch": (_I, [_VP, _VP, _U32, _VP, _VP]),
+    "cz_engine_add_connected_batch": (_I, [_VP, _VP, _U32, _VP, _VP]),
+    "cz_engine_remove_conns": (_I, [_VP, _U32, _VP, _VP]),
+    "cz_acceptor_release_batch": (_I, [_VP, _U32, _VP]),
+    "cz_connector_release_batch": (_I, [_VP, _U32, _VP]),
+    "cz_zmtp_metadata_check":(_I, [_VP, _U64, _I]),
     "cz_zmtp_metadata": (_U32, [_I, _VP, _U32, _VP, _U32]),
     "cz_last_error": (ctypes.c_char_p, []),
     "cz_version": (ctypes.c_char_p, []),

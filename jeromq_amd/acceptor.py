@@ -7,6 +7,7 @@ CurveServerMechanism's handshake (CurveServerMechanism.java:254-517) for many co
     acc.client_key(slot)                       # allow-list check before READY is sent
     c = engine.add_accepted(acc, slot)         # the session moves to the batching engine
     acc.release(slot)
+    ids = engine.add_accepted_many(acc, slots); acc.release_many(slots)   # the same for many slots at once
 
 Each stage is a fixed number of device launches and one synchronisation whatever the batch size
 (jeromq_amd/csrc/cz_acceptor.cpp).  Every item behaves as one CurveServerHandshake fed the same

@@ -7,6 +7,7 @@ CurveClientMechanism's handshake (CurveClientMechanism.java:246-429) for many co
     for (rc, event, slot, _), conn in zip(con.ready(slots, readys), conns): ...
     c = engine.add_connected(con, slot)        # the session moves to the batching engine
     con.release(slot)
+    ids = engine.add_connected_many(con, slots); con.release_many(slots)   # the same for many slots at once
 
 Each stage is a fixed number of device launches and one synchronisation whatever the batch size
 (jeromq_amd/csrc/cz_connector.cpp).  Every item behaves as one CurveClientHandshake fed the same

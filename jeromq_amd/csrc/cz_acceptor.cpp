@@ -342,6 +342,16 @@ int cz_engine_add_accepted(cz_engine *e, const cz_acceptor *a, int32_t slot)
 // (the device record holds s', the cookie key and cnPrecom)
 int cz_acceptor_release(cz_acceptor *a, int32_t slot) { return hs_release(a, "cz_acceptor_release", slot); }
 
+int cz_engine_add_accepted_batch(cz_engine *e, const cz_acceptor *a, uint32_t count, const int32_t *slots, int32_t *ids)
+{
+    return hs_engine_add_batch(e, a, "cz_engine_add_accepted_batch", count, slots, ids, CZA_STATE_PRECOM, NEXT_NONCE, 1);
+}
+
+int cz_acceptor_release_batch(cz_acceptor *a, uint32_t count, const int32_t *slots)
+{
+    return hs_release_batch(a, "cz_acceptor_release_batch", count, slots);
+}
+
 uint32_t cz_acceptor_pending(const cz_acceptor *a) { return hs_pending(a); }
 
 }  // extern "C"

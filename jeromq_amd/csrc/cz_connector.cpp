@@ -402,6 +402,16 @@ int cz_engine_add_connected(cz_engine *e, const cz_connector *c, int32_t slot)
 // (the device record holds c', kH, cnPrecom and kV)
 int cz_connector_release(cz_connector *c, int32_t slot) { return hs_release(c, "cz_connector_release", slot); }
 
+int cz_engine_add_connected_batch(cz_engine *e, const cz_connector *c, uint32_t count, const int32_t *slots, int32_t *ids)
+{
+    return hs_engine_add_batch(e, c, "cz_engine_add_connected_batch", count, slots, ids, CZC_STATE_PRECOM, NEXT_NONCE, 0);
+}
+
+int cz_connector_release_batch(cz_connector *c, uint32_t count, const int32_t *slots)
+{
+    return hs_release_batch(c, "cz_connector_release_batch", count, slots);
+}
+
 uint32_t cz_connector_pending(const cz_connector *c) { return hs_pending(c); }
 
 }  // extern "C"

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "cz_internal.h"
+#include "cz_session.h"
 
 // pipeline depth of a large flush: groups of >= 8 MiB of wire bytes, at most this many.  At 1 GiB
 // per flush, 16 against 8: out 39.0 -> 40.9, in 38.0 -> 40.0 GiB/s (shorter pipeline fill and
@@ -263,6 +264,10 @@ struct cz_engine {
     HostBuf h_status, h_nonces;
     HostBuf h_meta;  // pinned staging of descriptors / items / segment lists (async H2D)
     RxPool rxpool;   // every connection's receive buffer
+    // bulk add / remove (engine_add_sessions, cz_engine_remove_conns): staged precoms and job records, or the
+    // key indices to wipe; reused from call to call, wiped before each call returns
+    DevBuf d_stage;
+    HostBuf h_stage;
 
     // wait for everything issued on every stream (error paths of the flushes: the next recv /
     // flush may write or regrow the pinned buffers those copies still read or write)
@@ -288,9 +293,9 @@ struct cz_engine {
                 (void)hipStreamDestroy(q);
             }
         for (DevBuf *b : {&subkeys, &d_in, &d_body, &d_wire, &d_desc, &d_seg, &d_comb, &d_work, &d_items, &d_status,
-                          &d_nonces, &d_plain, &d_subs, &d_fruns, &d_fwaves})
+                          &d_nonces, &d_plain, &d_subs, &d_fruns, &d_fwaves, &d_stage})
             b->release();
-        for (HostBuf *b : {&arena, &h_wire, &h_plain, &h_status, &h_nonces, &h_meta})
+        for (HostBuf *b : {&arena, &h_wire, &h_plain, &h_status, &h_nonces, &h_meta, &h_stage})
             b->release();
     }
 
@@ -940,6 +945,108 @@ struct cz_engine {
     }
 };
 
+namespace czi {
+
+int engine_device(const cz_engine *e) { return e->device; }
+
+// Bulk session hand-over, the add side.  What a loop of cz_engine_add_conn does per connection
+// (hipMalloc, H2D, two k_subkeys launches, memset, synchronise, hipFree) is one chain for the batch:
+//   grow the subkey table once | H2D of the job records (and, staged, of the precoms) |
+//   k_session_subkeys | wipe the device staging | synchronise | wipe the pinned staging
+// Ids and key slots are planned first, exactly as the loop would hand them out (free_ids from the
+// back, then new ids in order), and the engine's tables change only after the synchronisation: a
+// failure hands out nothing.
+int engine_add_sessions(cz_engine *e, const char *where, uint32_t count, const SessionItem *items, const void *d_base,
+                        int32_t *ids)
+{
+    uint32_t nv = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        ids[i] = CZ_EINVAL;
+        nv += items[i].ok ? 1u : 0u;
+    }
+    if (nv == 0)
+        return CZ_OK;
+    auto all_failed = [&](int rc) {
+        for (uint32_t i = 0; i < count; i++)
+            ids[i] = rc;
+        return rc;
+    };
+    const uint32_t nfree = (uint32_t)e->free_ids.size();
+    const uint32_t nnew = nv - std::min(nv, nfree);
+    if (nnew > (0x7fffffffu - e->nkeys) / 2 || e->conns.size() + nnew > 0x7fffffffu)
+        return all_failed(fail(CZ_ENOMEM, "%s: %u more connections exceed the id range", where, nnew));
+    const bool staged = d_base == nullptr;
+    const uint64_t keys_b = staged ? 32ull * nv : 0, total = keys_b + (uint64_t)nv * sizeof(cz_session_job);
+    hipError_t he;
+    if ((he = hipSetDevice(e->device)) != hipSuccess || (nnew && (he = e->grow_keys(e->nkeys + 2 * nnew)) != hipSuccess) ||
+        (he = e->d_stage.reserve(total)) != hipSuccess || (he = e->h_stage.reserve(total)) != hipSuccess)
+        return all_failed(hip_fail(he, where));
+    uint8_t *hs = (uint8_t *)e->h_stage.ptr, *ds = (uint8_t *)e->d_stage.ptr;
+    cz_session_job *jobs = (cz_session_job *)(hs + keys_b);
+    uint32_t fr = nfree, nk = e->nkeys, j = 0;
+    int32_t next_id = (int32_t)e->conns.size();
+    for (uint32_t i = 0; i < count; i++) {
+        if (!items[i].ok)
+            continue;
+        uint32_t tx, rx;
+        if (fr) {  // a removed connection's id and key slots
+            ids[i] = e->free_ids[--fr];
+            tx = e->conns[(size_t)ids[i]].tx_key;
+            rx = e->conns[(size_t)ids[i]].rx_key;
+        } else {
+            ids[i] = next_id++;
+            tx = nk;
+            rx = nk + 1;
+            nk += 2;
+        }
+        if (staged)
+            memcpy(hs + 32ull * j, items[i].h_key, 32);
+        jobs[j] = {staged ? 32ull * j : items[i].src_off, tx, rx, items[i].server ? 1u : 0u, 0u};
+        j++;
+    }
+    if ((he = hipMemcpyAsync(ds, hs, total, hipMemcpyHostToDevice, e->stream)) != hipSuccess ||
+        (he = czk_session_subkeys((const cz_session_job *)(ds + keys_b), nv, staged ? ds : d_base, e->subkeys.ptr,
+                                  e->stream)) != hipSuccess ||
+        (he = hipMemsetAsync(ds, 0, total, e->stream)) != hipSuccess ||
+        (he = hipStreamSynchronize(e->stream)) != hipSuccess) {
+        // nothing is handed out: the table entries a lane may have written and the staging are wiped
+        uint8_t *table = (uint8_t *)e->subkeys.ptr;
+        if (nk > e->nkeys)
+            (void)hipMemsetAsync(table + 32ull * e->nkeys, 0, 32ull * (nk - e->nkeys), e->stream);
+        for (uint32_t k = 0; k < nv; k++)
+            if (jobs[k].tx_key < e->nkeys) {
+                (void)hipMemsetAsync(table + 32ull * jobs[k].tx_key, 0, 32, e->stream);
+                (void)hipMemsetAsync(table + 32ull * jobs[k].rx_key, 0, 32, e->stream);
+            }
+        (void)hipMemsetAsync(ds, 0, total, e->stream);
+        (void)hipStreamSynchronize(e->stream);
+        secure_wipe(hs, keys_b);
+        return all_failed(hip_fail(he, where));
+    }
+    secure_wipe(hs, keys_b);
+    j = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        if (!items[i].ok)
+            continue;
+        Conn c;
+        c.server = items[i].server != 0;
+        c.tx_key = jobs[j].tx_key;
+        c.rx_key = jobs[j].rx_key;
+        c.nonce = items[i].nonce;
+        c.peer_nonce = items[i].peer_nonce;
+        j++;
+        if ((size_t)ids[i] < e->conns.size())
+            e->conns[(size_t)ids[i]] = std::move(c);
+        else
+            e->conns.push_back(std::move(c));
+    }
+    e->free_ids.resize(fr);
+    e->nkeys = nk;
+    return CZ_OK;
+}
+
+}  // namespace czi
+
 extern "C" {
 
 int cz_engine_create(cz_engine **out, uint64_t arena_bytes, int device)
@@ -1041,6 +1148,84 @@ int cz_engine_remove_conn(cz_engine *e, int conn)
     dead.removed = true;
     *c = std::move(dead);
     e->free_ids.push_back(conn);
+    return CZ_OK;
+}
+
+int cz_engine_add_conns(cz_engine *e, uint32_t count, const uint8_t *as_server, const uint8_t *precoms,
+                        const uint64_t *cn_nonce, const uint64_t *cn_peer_nonce, int32_t *ids)
+{
+    if (!e)
+        return fail(CZ_EINVAL, "cz_engine_add_conns: null pointer");
+    if (count == 0)
+        return CZ_OK;
+    for (uint32_t i = 0; ids && i < count; i++)
+        ids[i] = CZ_EINVAL;
+    if (!precoms || !cn_nonce || !cn_peer_nonce || !ids)
+        return fail(CZ_EINVAL, "cz_engine_add_conns: null pointer");
+    std::vector<SessionItem> items(count);
+    for (uint32_t i = 0; i < count; i++)
+        items[i] = {1, (uint8_t)(as_server && as_server[i] ? 1 : 0), 0, precoms + 32ull * i, cn_nonce[i], cn_peer_nonce[i]};
+    return engine_add_sessions(e, "cz_engine_add_conns", count, items.data(), nullptr, ids);
+}
+
+// cz_engine_remove_conn for a list: the subkeys of every connection named are wiped by one
+// k_scatter_wipe launch behind one H2D of their table indices, with one synchronisation; the host
+// side of each removal follows in list order, so free_ids ends as the loop leaves it.
+int cz_engine_remove_conns(cz_engine *e, uint32_t count, const int *conns, int32_t *rcs)
+{
+    if (!e)
+        return fail(CZ_EINVAL, "cz_engine_remove_conns: null pointer");
+    if (count == 0)
+        return CZ_OK;
+    if (!conns || !rcs)
+        return fail(CZ_EINVAL, "cz_engine_remove_conns: null pointer");
+    hipError_t he;
+    if ((he = hipSetDevice(e->device)) != hipSuccess || (he = e->h_stage.reserve(8ull * count)) != hipSuccess ||
+        (he = e->d_stage.reserve(8ull * count)) != hipSuccess) {
+        std::fill(rcs, rcs + count, (int32_t)CZ_EHIP);
+        return hip_fail(he, "cz_engine_remove_conns");
+    }
+    // a connection is marked as it is named: a second mention finds it gone, as in the loop
+    uint32_t *idx = (uint32_t *)e->h_stage.ptr;
+    std::vector<int> hit;
+    for (uint32_t i = 0; i < count; i++) {
+        Conn *c = e->conn(conns[i]);
+        rcs[i] = c ? CZ_OK : CZ_EINVAL;
+        if (!c)
+            continue;
+        idx[2 * hit.size()] = c->tx_key;
+        idx[2 * hit.size() + 1] = c->rx_key;
+        c->removed = true;
+        hit.push_back(conns[i]);
+    }
+    if (hit.empty())
+        return CZ_OK;
+    const uint32_t nidx = 2 * (uint32_t)hit.size();
+    if ((he = hipMemcpyAsync(e->d_stage.ptr, idx, 4ull * nidx, hipMemcpyHostToDevice, e->stream)) != hipSuccess ||
+        (he = czk_scatter_wipe(e->subkeys.ptr, (const uint32_t *)e->d_stage.ptr, nidx, 32, 0, e->stream)) != hipSuccess ||
+        (he = hipStreamSynchronize(e->stream)) != hipSuccess) {
+        (void)hipStreamSynchronize(e->stream);
+        for (int id : hit)
+            e->conns[(size_t)id].removed = false;
+        std::fill(rcs, rcs + count, (int32_t)CZ_EHIP);
+        return hip_fail(he, "cz_engine_remove_conns");
+    }
+    e->pend.erase(std::remove_if(e->pend.begin(), e->pend.end(),
+                                 [e](const OutMsg &m) { return e->conns[m.conn].removed; }),
+                  e->pend.end());
+    for (int id : hit) {
+        Conn &c = e->conns[(size_t)id];
+        if (c.rx.ptr) {
+            explicit_bzero(c.rx.ptr, c.rx_len);
+            e->rxpool.free_list.push_back(c.rx);
+        }
+        Conn dead;
+        dead.tx_key = c.tx_key;
+        dead.rx_key = c.rx_key;
+        dead.removed = true;
+        c = std::move(dead);
+        e->free_ids.push_back(id);
+    }
     return CZ_OK;
 }
 

@@ -13,12 +13,14 @@
 #pragma once
 #include <sys/random.h>
 
+#include <algorithm>
 #include <cstring>
 #include <initializer_list>
 #include <vector>
 
 #include "cz_hs_records.h"
 #include "cz_internal.h"
+#include "cz_session.h"
 
 namespace czi {
 
@@ -68,6 +70,8 @@ struct HsBatch {
     DevBuf work;                      // a stage's jobs, records, key agreements and output
     HostBuf h_in, h_out;              // pinned staging of the same
     std::vector<uint32_t> item;       // lane -> index of its command in the caller's batch
+    DevBuf d_rel;                     // hs_release_batch: the slots whose records one launch wipes
+    HostBuf h_rel;                    // pinned staging of the same
 
     HsBatch(const char *name, uint32_t state_size) : name(name), state_size(state_size) {}
     HsBatch(const HsBatch &) = delete;
@@ -96,6 +100,8 @@ struct HsBatch {
         work.release();
         h_in.release();
         h_out.release();
+        d_rel.release();
+        h_rel.release();
     }
 
     Slot *slot(int32_t id) { return id >= 0 && (uint32_t)id < max_pending ? &slots[(size_t)id] : nullptr; }
@@ -202,6 +208,83 @@ int hs_engine_add(cz_engine *e, const HsBatch<Slot> *b, const char *session_name
     rc = cz_engine_add_conn(e, server, k, n, pn);
     secure_wipe(k, 32);
     return rc;
+}
+
+// The sessions of `count` slots as connections of the batching engine in one device chain
+// (engine_add_sessions, cz_engine.cpp).  cnPrecom never leaves the device: it lies in the slot's
+// record of `state`, at precom_off, from the stage that agreed it until the slot is released, and
+// k_session_subkeys reads it there.  The stage that made the slot CONNECTED has synchronised the
+// handshake's stream, so the engine's stream may read the record; this call returns after the engine's
+// synchronisation, so a release issued afterwards on the handshake's stream cannot overtake the read.
+// A handshake on another device than the engine has no record the engine's kernels can address: the
+// host slot table's precom is staged as cz_engine_add_conns stages its keys (that branch needs two
+// GPUs and is not covered by the single-GPU tests).  A slot that is out of range or not CONNECTED
+// gives ids[i] = CZ_EINVAL and consumes no id.
+template <class Slot>
+int hs_engine_add_batch(cz_engine *e, const HsBatch<Slot> *b, const char *where, uint32_t count, const int32_t *slots,
+                        int32_t *ids, uint32_t precom_off, uint64_t next_nonce, int server)
+{
+    if (!e || !b)
+        return fail(CZ_EINVAL, "%s: null pointer", where);
+    if (count == 0)
+        return CZ_OK;
+    for (uint32_t i = 0; ids && i < count; i++)
+        ids[i] = CZ_EINVAL;
+    if (!slots || !ids)
+        return fail(CZ_EINVAL, "%s: null pointer", where);
+    const bool direct = b->device == engine_device(e) && b->state.ptr;
+    std::vector<SessionItem> items(count);
+    for (uint32_t i = 0; i < count; i++) {
+        const Slot *s = b->slot(slots[i]);
+        if (!s || s->state != SLOT_CONNECTED) {
+            items[i] = SessionItem{0, 0, 0, nullptr, 0, 0};
+            continue;
+        }
+        items[i] = SessionItem{1, (uint8_t)(server ? 1 : 0), (uint64_t)b->state_size * (uint32_t)slots[i] + precom_off,
+                               s->precom, next_nonce, s->peer_nonce};
+    }
+    return engine_add_sessions(e, where, count, items.data(), direct ? b->state.ptr : nullptr, ids);
+}
+
+// hs_release for a list, all or nothing: every slot must be in use and none named twice, else
+// CZ_EINVAL with nothing released.  The device records are wiped by one k_scatter_wipe launch on the
+// handshake's stream, before any later stage can hand a slot to another connection; the slots are
+// freed in list order.
+template <class Slot>
+int hs_release_batch(HsBatch<Slot> *b, const char *where, uint32_t count, const int32_t *slots)
+{
+    if (!b)
+        return fail(CZ_EINVAL, "%s: null pointer", where);
+    if (count == 0)
+        return CZ_OK;
+    if (!slots)
+        return fail(CZ_EINVAL, "%s: null pointer", where);
+    for (uint32_t i = 0; i < count; i++) {
+        const Slot *s = b->slot(slots[i]);
+        if (!s || s->state == SLOT_FREE)
+            return fail(CZ_EINVAL, "%s: slot %d is not in use", where, slots[i]);
+    }
+    {
+        std::vector<int32_t> sorted(slots, slots + count);
+        std::sort(sorted.begin(), sorted.end());
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end())
+            return fail(CZ_EINVAL, "%s: slot %d is named twice", where, *dup);
+    }
+    hipError_t e;
+    if ((e = hipSetDevice(b->device)) != hipSuccess || (e = b->h_rel.reserve(4ull * count)) != hipSuccess ||
+        (e = b->d_rel.reserve(4ull * count)) != hipSuccess)
+        return hip_fail(e, where);
+    memcpy(b->h_rel.ptr, slots, 4ull * count);  // checked above: every id is in [0, max_pending)
+    // (the synchronisation lets the next call reuse the pinned list)
+    if ((e = hipMemcpyAsync(b->d_rel.ptr, b->h_rel.ptr, 4ull * count, hipMemcpyHostToDevice, b->stream)) != hipSuccess ||
+        (e = czk_scatter_wipe(b->state.ptr, (const uint32_t *)b->d_rel.ptr, count, b->state_size, 0, b->stream)) !=
+            hipSuccess ||
+        (e = hipStreamSynchronize(b->stream)) != hipSuccess)
+        return hip_fail(e, where);
+    for (uint32_t i = 0; i < count; i++)
+        b->free_slot(slots[i]);
+    return CZ_OK;
 }
 
 template <class Slot>

@@ -43,6 +43,7 @@
 
 #include "cz_device.h"
 #include "cz_diag.h"
+#include "cz_session.h"
 #include "../../include/curvezmq_mi355x.h"
 
 // The file compiles as one translation unit (CZ_KPART undefined) or as three that build in parallel
@@ -3727,6 +3728,46 @@ __global__ __launch_bounds__(BLOCK) void k_subkeys(const uint8_t *__restrict__ p
             op[4 * w + b] = (uint8_t)(o[w] >> (8 * b));
 }
 
+// Bulk session hand-over (cz_session.h): lane 2j derives session j's tx subkey, lane 2j + 1 its rx
+// subkey.  The server seals under "CurveZMQMESSAGES" and opens under "...MESSAGEC", the client the
+// other way round (prefix_for); the two prefixes differ in their last byte.  cnPrecom is read where it
+// lies, in the handshake's state record or the staged array, with two 16-byte loads, and the subkey
+// goes to the job's own table slot with two 16-byte stores.
+__global__ __launch_bounds__(BLOCK) void k_session_subkeys(const cz_session_job *__restrict__ jobs, uint32_t nlanes,
+                                                            const uint8_t *__restrict__ base,
+                                                            uint8_t *__restrict__ table)
+{
+    const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= nlanes)
+        return;
+    const cz_session_job job = jobs[t >> 1];
+    const uint32_t rx = t & 1u;
+    const uint4 *kp = reinterpret_cast<const uint4 *>(base + job.src_off);
+    const uint4 ka = kp[0], kb = kp[1];
+    const u32 k[8] = {ka.x, ka.y, ka.z, ka.w, kb.x, kb.y, kb.z, kb.w};
+    // "Curv" "eZMQ" "MESS" "AGES" / "AGEC", little-endian words
+    const bool s2c = (job.server != 0u) != (rx != 0u);
+    const u32 in4[4] = {0x76727543u, 0x514d5a65u, 0x5353454du, s2c ? 0x53454741u : 0x43454741u};
+    u32 o[8];
+    hsalsa20(o, k, in4);
+    uint4 *op = reinterpret_cast<uint4 *>(table + 32ull * (rx ? job.rx_key : job.tx_key));
+    op[0] = make_uint4(o[0], o[1], o[2], o[3]);
+    op[1] = make_uint4(o[4], o[5], o[6], o[7]);
+}
+
+// Zero records by index: lane t clears 16 bytes, chunk t % (rec_bytes / 16) of record idx[t / (rec_bytes / 16)]
+// of the table at `base` (records of rec_bytes bytes).  The subkey wipe of a bulk remove (32-byte
+// records) and the slot-record wipe of a bulk release (128-byte records).
+__global__ __launch_bounds__(BLOCK) void k_scatter_wipe(uint8_t *__restrict__ base, const uint32_t *__restrict__ idx,
+                                                         uint64_t nchunks, uint32_t rec_chunks)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= nchunks)
+        return;
+    const uint64_t r = t / rec_chunks, c = t - r * rec_chunks;
+    *reinterpret_cast<uint4 *>(base + 16ull * ((uint64_t)idx[r] * rec_chunks + c)) = make_uint4(0u, 0u, 0u, 0u);
+}
+
 // Synthetic payload generator: counter-based SplitMix64 words (tests/cz_testlib.py splitmix_words).
 __device__ __forceinline__ u64 splitmix(u64 seed, u64 idx)
 {
@@ -4205,6 +4246,34 @@ hipError_t czk_subkeys(const void *precom, void *out, uint32_t nkeys, const uint
     dim3 grid((nkeys + BLOCK - 1) / BLOCK);
     hipLaunchKernelGGL(k_subkeys, grid, dim3(BLOCK), 0, s, (const uint8_t *)precom, (uint8_t *)out, nkeys, p[0], p[1],
                        p[2], p[3]);
+    return hipGetLastError();
+}
+
+hipError_t czk_session_subkeys(const cz_session_job *jobs, uint32_t count, const void *base, void *table, hipStream_t s)
+{
+    if (count == 0)
+        return hipSuccess;
+    if (count > 0x7fffffffu)
+        return hipErrorInvalidValue;
+    const uint32_t nlanes = 2u * count;
+    hipLaunchKernelGGL(k_session_subkeys, dim3((nlanes + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, jobs, nlanes,
+                       (const uint8_t *)base, (uint8_t *)table);
+    return hipGetLastError();
+}
+
+hipError_t czk_scatter_wipe(void *base, const uint32_t *idx, uint32_t count, uint32_t rec_bytes, uint64_t offset,
+                            hipStream_t s)
+{
+    if (count == 0)
+        return hipSuccess;
+    if (rec_bytes == 0 || rec_bytes % 16u || (((uintptr_t)base + offset) & 15u))
+        return hipErrorInvalidValue;
+    const uint32_t rec_chunks = rec_bytes / 16u;
+    const uint64_t nchunks = (uint64_t)count * rec_chunks, blocks = (nchunks + BLOCK - 1) / BLOCK;
+    if (blocks > 0x7fffffffull)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scatter_wipe, dim3((uint32_t)blocks), dim3(BLOCK), 0, s, (uint8_t *)base + offset, idx, nchunks,
+                       rec_chunks);
     return hipGetLastError();
 }
 

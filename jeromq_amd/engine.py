@@ -4,6 +4,7 @@ device batch per flush and socket-ready ZMTP v2 wire streams per connection.
 
     eng = CurveBatchEngine(arena_bytes=1 << 26)
     c = eng.add_connection(precom, as_server=False)          # CurveClientMechanism state
+    ids = eng.add_accepted_many(acceptor, slots)              # N finished handshakes, one device chain
     eng.send(c, b"payload", more=False)
     eng.publish([c, c2, c3], b"payload")                      # one payload to many (PUB fan-out)
     eng.flush_out(); wire = eng.wire_out(c)                   # bytes for the socket
@@ -12,6 +13,8 @@ device batch per flush and socket-ready ZMTP v2 wire streams per connection.
     eng.error(c)                                              # (CZ_EPROTO, ZMTP event) after a failure
 """
 import ctypes
+
+import numpy as np
 
 from . import _lib
 
@@ -76,6 +79,65 @@ class CurveBatchEngine:
         """The connection is gone (StreamEngine teardown): queued messages and received bytes are
         dropped, its subkeys wiped, and its id reused by a later add_connection."""
         _lib.check(self._L.cz_engine_remove_conn(self._h, conn), "cz_engine_remove_conn")
+
+    # ---- bulk session hand-over: N sessions per call, one device chain whatever N is ----
+
+    def add_connections(self, precoms, as_server=False, cn_nonce=None, cn_peer_nonce=None):
+        """add_connection for many sessions at once -> [id]: the ids a loop of add_connection would
+        return.  as_server: one flag for all or one per session; cn_nonce / cn_peer_nonce: None (the
+        defaults of add_connection per role), one value for all or one per session."""
+        keys = [bytes(k) for k in precoms]
+        n = len(keys)
+        if any(len(k) != 32 for k in keys):
+            raise ValueError("every precom is 32 bytes")
+        roles = [bool(as_server)] * n if isinstance(as_server, (bool, int)) else [bool(r) for r in as_server]
+
+        def per_item(v, server_default, client_default):
+            if v is None:
+                return [server_default if r else client_default for r in roles]
+            return [int(v)] * n if isinstance(v, int) else [int(x) for x in v]
+        nonce, peer = per_item(cn_nonce, 2, 3), per_item(cn_peer_nonce, 2, 1)
+        if not (len(roles) == len(nonce) == len(peer) == n):
+            raise ValueError("one role and one nonce pair per precom")
+        if n == 0:
+            return []
+        ids = np.empty(n, dtype=np.int32)
+        rc = self._L.cz_engine_add_conns(self._h, n, np.array(roles, dtype=np.uint8).ctypes.data_as(ctypes.c_void_p),
+                                         b"".join(keys), np.array(nonce, dtype=np.uint64).ctypes.data_as(ctypes.c_void_p),
+                                         np.array(peer, dtype=np.uint64).ctypes.data_as(ctypes.c_void_p),
+                                         ids.ctypes.data_as(ctypes.c_void_p))
+        _lib.check(rc, "cz_engine_add_conns")
+        return ids.tolist()
+
+    def _add_many(self, fn, handshake, slots):
+        arr = np.array(list(slots), dtype=np.int32)
+        if len(arr) == 0:
+            return []
+        ids = np.empty(len(arr), dtype=np.int32)
+        _lib.check(getattr(self._L, fn)(self._h, handshake._h, len(arr), arr.ctypes.data_as(ctypes.c_void_p),
+                                        ids.ctypes.data_as(ctypes.c_void_p)), fn)
+        return ids.tolist()
+
+    def add_accepted_many(self, acceptor, slots):
+        """add_accepted for many slots at once -> [id]; a slot without a completed handshake gives a
+        negative entry (CZ_EINVAL), consumes no id and does not raise.  The session keys are read from
+        the acceptor's device state; the slots may be released as soon as this returns."""
+        return self._add_many("cz_engine_add_accepted_batch", acceptor, slots)
+
+    def add_connected_many(self, connector, slots):
+        """add_connected for many slots at once -> [id], as add_accepted_many."""
+        return self._add_many("cz_engine_add_connected_batch", connector, slots)
+
+    def remove_connections(self, conns):
+        """remove_connection for a list -> [rc]: CZ_OK, or CZ_EINVAL for an id that is unknown, already
+        removed or named before in the list (the others are removed)."""
+        arr = np.array(list(conns), dtype=np.int32)
+        if len(arr) == 0:
+            return []
+        rcs = np.empty(len(arr), dtype=np.int32)
+        _lib.check(self._L.cz_engine_remove_conns(self._h, len(arr), arr.ctypes.data_as(ctypes.c_void_p),
+                                                  rcs.ctypes.data_as(ctypes.c_void_p)), "cz_engine_remove_conns")
+        return rcs.tolist()
 
     def msg_alloc(self, n):
         """Pinned payload buffer in the engine arena (ZMQ_MSG_ALLOCATOR); a ctypes array or None."""

@@ -19,7 +19,14 @@ WELCOMEs and READYs come from the CPU model, outside the timed region, for the i
 secrets and vouch nonces of POOL connections of one client; the baseline is 64 cz_hs clients one after
 another, constructor through READY.  `hello_getrandom_ms` is stage 1 drawing its secrets from getrandom.
 
-Writes one JSON (default profiles/hs_batch/hs_batch.json, or hs_connect.json for the client) and prints it."""
+--handover times what follows the handshake instead: N accepted sessions into the batching engine and out
+of the acceptor's slot table, per slot (cz_engine_add_accepted + cz_acceptor_release in a loop) against
+the bulk calls (cz_engine_add_accepted_batch + cz_acceptor_release_batch), the same for
+cz_engine_remove_conn against cz_engine_remove_conns, and the two handshake stages beside them
+(handover_main).
+
+Writes one JSON (default profiles/hs_batch/hs_batch.json, hs_connect.json for the client, hs_handover.json
+for --handover) and prints it."""
 import argparse
 import ctypes
 import json
@@ -270,15 +277,128 @@ def client_main(args):
     print(json.dumps(out))
 
 
+HANDOVER_SIZES = (64, 1024, 16384, 65536)
+# what "--handover" was written to find out, fixed before the first run; each is marked from the run
+HANDOVER_HYPOTHESES = (
+    ("batch_10x_from_1024", "(b) the bulk add + release is at least 10x below (a) the per-slot loop from N = 1024"),
+    ("handover_minor_share", "after the change the hand-over (b) is a minor share of a storm: at most a quarter of "
+                             "stage 1 + stage 2 at every N"),
+)
+
+
+def handover_main(args):
+    """The last step of a storm: N accepted sessions into the engine and out of the acceptor's table, and
+    out of the engine again.  Per round, for each N, both ways in turn (which goes first alternates):
+      (a) loop of cz_engine_add_accepted + cz_acceptor_release   | (b) cz_engine_add_accepted_batch + cz_acceptor_release_batch
+      (c) loop of cz_engine_remove_conn                           |     cz_engine_remove_conns
+    each behind its own stage 1 + stage 2 (timed, (d)), on its own engine so that both see the same
+    history; round 0 warms up (tables and staging grow), then the median of --reps rounds."""
+    import torch
+    from jeromq_amd import _lib
+    assert torch.cuda.is_available(), "hs_bench needs a GPU"
+    L = _lib.lib()
+    pool = make_pool()
+    out = {"device": torch.cuda.get_device_name(0), "what": "handover", "reps": args.reps, "pool": POOL,
+           "clock": "time.perf_counter", "rows": []}
+    for n in args.sizes:
+        acc = ctypes.c_void_p()
+        _lib.check(L.cz_acceptor_create(ctypes.byref(acc), SERVER_SEC, 0, None, 0, n, 0), "cz_acceptor_create")
+        engines = {}
+        for leg in ("loop", "batch"):
+            h = ctypes.c_void_p()
+            _lib.check(L.cz_engine_create(ctypes.byref(h), 4096, 0), "cz_engine_create")
+            engines[leg] = h
+        b = Batch(pool, n)
+        ids = np.zeros(n, dtype=np.int32)
+        rcs = np.zeros(n, dtype=np.int32)
+        t = {k: [] for k in ("stage1", "stage2", "loop_add", "batch_add", "loop_remove", "batch_remove")}
+
+        def loop_leg(eng):
+            slots = b.slots.tolist()
+            t0 = time.perf_counter()
+            got = [L.cz_engine_add_accepted(eng, acc, s) for s in slots]
+            for s in slots:
+                L.cz_acceptor_release(acc, s)
+            t1 = time.perf_counter()
+            assert min(got) >= 0 and L.cz_acceptor_pending(acc) == 0
+            t2 = time.perf_counter()
+            bad = sum(L.cz_engine_remove_conn(eng, c) for c in got)
+            t3 = time.perf_counter()
+            assert bad == 0
+            return t1 - t0, t3 - t2
+
+        def batch_leg(eng):
+            t0 = time.perf_counter()
+            rc1 = L.cz_engine_add_accepted_batch(eng, acc, n, b.slots.ctypes.data, ids.ctypes.data)
+            rc2 = L.cz_acceptor_release_batch(acc, n, b.slots.ctypes.data)
+            t1 = time.perf_counter()
+            assert rc1 == 0 and rc2 == 0 and ids.min() >= 0 and L.cz_acceptor_pending(acc) == 0
+            t2 = time.perf_counter()
+            rc3 = L.cz_engine_remove_conns(eng, n, ids.ctypes.data, rcs.ctypes.data)
+            t3 = time.perf_counter()
+            assert rc3 == 0 and not rcs.any()
+            return t1 - t0, t3 - t2
+
+        for rep in range(args.reps + 1):
+            order = ("loop", "batch") if rep % 2 else ("batch", "loop")
+            for leg in order:
+                s1 = b.stage1(L, acc)
+                s2 = b.stage2(L, acc)
+                add, rem = (loop_leg if leg == "loop" else batch_leg)(engines[leg])
+                if rep:
+                    t["stage1"].append(s1)
+                    t["stage2"].append(s2)
+                    t[leg + "_add"].append(add)
+                    t[leg + "_remove"].append(rem)
+        for h in engines.values():
+            L.cz_engine_destroy(h)
+        L.cz_acceptor_destroy(acc)
+        med = {k: statistics.median(v) * 1e3 for k, v in t.items()}
+        hs = med["stage1"] + med["stage2"]
+        row = {"n": n, "stage1_ms": round(med["stage1"], 4), "stage2_ms": round(med["stage2"], 4),
+               "loop_add_release_ms": round(med["loop_add"], 4), "batch_add_release_ms": round(med["batch_add"], 4),
+               "loop_remove_ms": round(med["loop_remove"], 4), "batch_remove_ms": round(med["batch_remove"], 4),
+               "add_release_speedup": round(med["loop_add"] / med["batch_add"], 2),
+               "remove_speedup": round(med["loop_remove"] / med["batch_remove"], 2),
+               "handover_over_handshake_before": round(med["loop_add"] / hs, 4),
+               "handover_over_handshake_after": round(med["batch_add"] / hs, 4),
+               "all_ms": {k: [round(x * 1e3, 4) for x in v] for k, v in t.items()}}
+        out["rows"].append(row)
+        print(f"n={n}: stages {hs:.3f} ms; add+release loop {med['loop_add']:.3f} ms, bulk {med['batch_add']:.3f} ms; "
+              f"remove loop {med['loop_remove']:.3f} ms, bulk {med['batch_remove']:.3f} ms", file=sys.stderr)
+    verdicts = {
+        "batch_10x_from_1024": all(r["add_release_speedup"] >= 10 for r in out["rows"] if r["n"] >= 1024),
+        "handover_minor_share": all(r["handover_over_handshake_after"] <= 0.25 for r in out["rows"]),
+    }
+    out["hypotheses"] = [{"id": k, "statement": s, "verdict": "confirmed" if verdicts[k] else "contradicted"}
+                         for k, s in HANDOVER_HYPOTHESES]
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--side", choices=("server", "client"), default="server")
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--sizes", type=int, nargs="*", default=list(SIZES))
+    ap.add_argument("--handover", action="store_true",
+                    help="time the session hand-over (acceptor -> engine -> gone), per slot against bulk, beside the "
+                         "two handshake stages; N = 64, 1024, 16384, 65536, median of 7; writes hs_handover.json")
+    ap.add_argument("--reps", type=int, default=None)
+    ap.add_argument("--sizes", type=int, nargs="*", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 7 if args.handover else 5
+    if args.sizes is None:
+        args.sizes = list(HANDOVER_SIZES if args.handover else SIZES)
     if args.reps < 5:
         ap.error("--reps must be at least 5")
+    if args.handover:
+        if args.out is None:
+            args.out = os.path.join(ROOT, "profiles", "hs_batch", "hs_handover.json")
+        return handover_main(args)
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "hs_batch",
                                 "hs_connect.json" if args.side == "client" else "hs_batch.json")
