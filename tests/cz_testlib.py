@@ -156,15 +156,28 @@ class V2DecoderModel:
         self.pos = 0                 # bytes of the stream consumed so far
         self.msgs, self.error = [], None
         self.flags = self.size = self.body_off = 0
+        self.got = 0                 # body bytes seen so far (bodies are counted, not kept)
 
     def feed(self, data):
-        for b in bytes(data):
+        data = bytes(data)
+        i = 0
+        while i < len(data):
             if self.error:
                 return
-            self.tmp += bytes([b])
-            self.pos += 1
-            if len(self.tmp) < self.need:
-                continue
+            if self.state == "body":   # a body is skipped in one step, whatever its size
+                take = min(self.need - self.got, len(data) - i)
+                self.got += take
+                self.pos += take
+                i += take
+                if self.got < self.need:
+                    continue
+                self.got = 0
+            else:
+                self.tmp += data[i:i + 1]
+                self.pos += 1
+                i += 1
+                if len(self.tmp) < self.need:
+                    continue
             if self.state == "flags":
                 first = self.tmp[0]
                 self.flags = (1 if first & 1 else 0) | (2 if first & 4 else 0)
