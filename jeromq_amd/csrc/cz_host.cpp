@@ -17,25 +17,7 @@
 
 #include "../../include/curvezmq_mi355x.h"
 #include "cz_internal.h"
-
-extern "C" {
-hipError_t czk_seal_uniform_box(const void *, uint64_t, void *, uint64_t, uint32_t, uint32_t, const void *, uint64_t,
-                                hipStream_t);
-hipError_t czk_seal_uniform(const void *, uint64_t, void *, uint64_t, uint32_t, uint32_t, const void *, uint64_t,
-                            const uint8_t *, hipStream_t);
-hipError_t czk_seal_fanout(const void *, uint32_t, uint32_t, const cz_fanout_sub *, const void *, void *, uint64_t,
-                           uint32_t, hipStream_t);
-hipError_t czk_seal_desc(const cz_frame_desc *, const uint32_t *, uint32_t, const void *, void *, const void *,
-                         hipStream_t);
-hipError_t czk_open_desc(const cz_frame_desc *, const uint32_t *, uint32_t, const void *, void *, const void *,
-                         uint16_t *, uint64_t *, hipStream_t);
-hipError_t czk_open_uniform(const void *, uint64_t, void *, uint64_t, uint32_t, uint32_t, const void *, uint64_t, int,
-                            uint16_t *, hipStream_t);
-hipError_t czk_fill(void *, uint64_t, uint64_t, hipStream_t);
-hipError_t czk_copy16(void *, const void *, uint64_t, hipStream_t);
-int czk_tune(const char *, int);
-int czk_owns_slots(uint64_t);
-}
+#include "cz_launch.h"
 
 namespace czi {
 
@@ -261,9 +243,9 @@ uint64_t nacl_one_bytes()
 // for its 65 blocks, where the segment plan spreads them ("PUB fan-out").  2^18
 // is the smallest measured count at which such a launch is throughput-bound and ahead of the segment
 // kernels at 4 KiB.
-static std::atomic<uint32_t> g_fanout_min{1u << 18};
+static std::atomic<uint64_t> g_fanout_min{1u << 18};
 
-uint32_t fanout_min() { return g_fanout_min.load(std::memory_order_relaxed); }
+uint32_t fanout_min() { return (uint32_t)g_fanout_min.load(std::memory_order_relaxed); }
 
 // cz_engine_flush_out: a publish's run of at least 64 frames (one full wave) whose payload is at most
 // this many bytes also leaves the segment plan, unless fanout_min is 0; 0 = rule off (cz_tune
@@ -278,9 +260,9 @@ uint32_t fanout_min() { return g_fanout_min.load(std::memory_order_relaxed); }
 //   1024  0.0382 / 0.0210   0.0395 / 0.0317   0.1522 / 0.1641  (loses below 2^18 lanes; flush 7.57 / 9.33)
 //   4096  0.1331 / 0.0362   0.1368 / 0.0635   0.5998 / 0.5764  (loses everywhere; flush 21.4 / 22.1)
 // Above a few blocks one lane per subscriber is held to that lane's serial walk.
-static std::atomic<uint32_t> g_fanout_short{256};
+static std::atomic<uint64_t> g_fanout_short{256};
 
-uint32_t fanout_short() { return g_fanout_short.load(std::memory_order_relaxed); }
+uint32_t fanout_short() { return (uint32_t)g_fanout_short.load(std::memory_order_relaxed); }
 
 // NaCl box/open of one message on the device.  A MESSAGE is the NaCl box of
 // 0^32 || flags || payload, so m[32] rides as the flags byte and m[33:] as the payload; for open
@@ -553,22 +535,16 @@ const char *cz_version(void) { return "curvezmq-mi355x 0.1 (gfx950)"; }
 
 int cz_tune(const char *key, int value)
 {
-    if (key && strcmp(key, "nacl_one_max") == 0) {  // bytes; at least one pass of k_nacl_one
-        const int old = (int)g_nacl_one_bytes.load(std::memory_order_relaxed);
-        g_nacl_one_bytes.store(std::min<uint64_t>(std::max<int64_t>(value, 0), czk_nacl_one_limit()),
-                               std::memory_order_relaxed);
-        return old;
-    }
-    if (key && strcmp(key, "fanout_min") == 0) {
-        const int old = (int)g_fanout_min.load(std::memory_order_relaxed);
-        g_fanout_min.store((uint32_t)std::max(value, 0), std::memory_order_relaxed);
-        return old;
-    }
-    if (key && strcmp(key, "fanout_short") == 0) {
-        const int old = (int)g_fanout_short.load(std::memory_order_relaxed);
-        g_fanout_short.store((uint32_t)std::max(value, 0), std::memory_order_relaxed);
-        return old;
-    }
+    // the host's own knobs (relaxed atomics: IO threads read them), then the kernels' (czk_tune)
+    const struct { const char *name; std::atomic<uint64_t> *knob; uint64_t max; } host_knobs[] = {
+        {"nacl_one_max", &g_nacl_one_bytes, czk_nacl_one_limit()},  // bytes; at least one pass of k_nacl_one
+        {"fanout_min", &g_fanout_min, INT32_MAX}, {"fanout_short", &g_fanout_short, INT32_MAX}};
+    for (const auto &h : host_knobs)
+        if (key && strcmp(key, h.name) == 0) {
+            const int old = (int)h.knob->load(std::memory_order_relaxed);
+            h.knob->store(std::min<uint64_t>((uint64_t)std::max(value, 0), h.max), std::memory_order_relaxed);
+            return old;
+        }
     int old = czk_tune(key, value);
     if (old < 0)
         return fail(CZ_EINVAL, "cz_tune: unknown key");

@@ -11,27 +11,7 @@
 
 #include "../../include/curvezmq_mi355x.h"
 #include "cz_hs_parse.h"
-
-extern "C" {
-hipError_t czk_seal_desc(const cz_frame_desc *, const uint32_t *, uint32_t, const void *, void *, const void *,
-                         hipStream_t);
-hipError_t czk_open_desc(const cz_frame_desc *, const uint32_t *, uint32_t, const void *, void *, const void *,
-                         uint16_t *, uint64_t *, hipStream_t);
-hipError_t czk_seal_fanout(const void *, uint32_t, uint32_t, const cz_fanout_sub *, const void *, void *, uint64_t,
-                           uint32_t, hipStream_t);
-int czk_fanout_class(uint64_t, uint32_t, uint32_t, int);
-hipError_t czk_seal_fanout_runs(const cz_fanout_run *, const cz_fanout_wave *, const uint32_t *, uint32_t, const void *,
-                                const cz_fanout_sub *, const void *, void *, hipStream_t);
-hipError_t czk_subkeys(const void *, void *, uint32_t, const uint8_t *, hipStream_t);
-hipError_t czk_seal_segments(const cz_frame_desc *, const cz_segment *, uint32_t, const cz_combine *, uint32_t,
-                             const void *, void *, const void *, void *, hipStream_t);
-hipError_t czk_open_segments(const cz_frame_desc *, const cz_segment *, uint32_t, const cz_combine *, uint32_t,
-                             const void *, void *, const void *, void *, uint16_t *, uint64_t *, hipStream_t);
-hipError_t czk_v2_copy(const cz_v2_item *, uint32_t, const void *, void *, hipStream_t);
-hipError_t czk_nacl_one(void *, uint32_t, int, void *, int, uint32_t, const uint8_t *, const uint8_t *, hipStream_t);
-uint32_t czk_nacl_one_max(void);
-uint32_t czk_nacl_one_limit(void);
-}
+#include "cz_launch.h"
 
 namespace czi {
 

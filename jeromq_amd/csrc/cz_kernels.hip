@@ -43,6 +43,8 @@
 
 #include "cz_device.h"
 #include "cz_diag.h"
+#include "cz_dispatch.h"
+#include "cz_launch.h"
 #include "cz_session.h"
 #include "../../include/curvezmq_mi355x.h"
 
@@ -55,18 +57,15 @@
 #define CZ_KPART_HAS(n) (CZ_KPART == 0 || CZ_KPART == (n))
 
 using namespace cz;
+// Mode, Staging, the launch geometry (BLOCK, WAVES, the emitters' LDS bytes) and the stride and size
+// limits: cz_dispatch.h, which the launchers' decisions share with the kernels
+using namespace czd;
 
 namespace {
-
-// MODE_BOX: MESSAGE output (as MODE_ZMQ) from input already in the reference's box layout,
-// m = 0^32 || flags || payload (CurveClientMechanism.java:144-153 builds exactly this and hands it
-// to Curve.afternm): box blocks are read where they lie, no funnel shift, no carried words.
-enum Mode { MODE_ZMQ = 0, MODE_NACL = 1, MODE_BOX = 2 };
 
 // "\x07MESSAGE" as two little-endian words
 constexpr u32 HDR0 = 0x53454d07u, HDR1 = 0x45474153u;
 
-constexpr int BLOCK = 256;              // threads per workgroup (4 waves)
 // Build-time occupancy knobs (CZ_EXTRA_FLAGS): CZ_UNIFORM_WAVES_PER_EU=n caps the VGPRs of the
 // uniform seal/open kernels so that n waves fit per SIMD, CZ_SEG_WAVES_PER_EU=n the segment
 // kernel's; CZ_SEAL_WAVES_PER_EU=n sets both.
@@ -109,10 +108,6 @@ constexpr int BLOCK = 256;              // threads per workgroup (4 waves)
 #else
 #define CZ_SEG_OCC
 #endif
-constexpr int WAVES = BLOCK / 64;
-constexpr u32 LINE_LDS_BYTES = 64 * 128; // EmitLines: one 128-byte line per frame
-constexpr u32 HOLD_LDS_BYTES = 64 * 64;  // EmitLines (seal): block 1 of every frame, until tag()
-constexpr u32 REGION_MAX = 16384;       // EmitRegion: 64 slots per wave
 
 struct V4 {
     u32 x, y, z, w;
@@ -1506,18 +1501,8 @@ __device__ void zero_bytes(uint8_t *p, u32 n)
 // -- its first and last, the tag slot -- are clipped to its bytes (st_range16): neighbouring
 // outputs own the other bytes.  emit/finish/close must be reached by all 64 lanes together:
 // ds_bpermute from an inactive lane returns garbage, not its base.
-constexpr u32 SROW = 208;  // 16 headroom + 192 bytes used; 52 dwords apart: conflict-free 16-lane b128
-constexpr u32 SHIFT_LDS_BYTES = 64 * SROW;  // EmitShiftLines: 13 KiB per wave
+// (rows of SROW bytes, SHIFT_LDS_BYTES per wave, and the flag bits of `te` above SHIFT_TOTAL_MAX: cz_dispatch.h)
 constexpr u32 SHEAD = 16;  // row bytes before line-space byte 0 (a chunk's first dword may start 4 early)
-// the uniform seal's rows (EmitShiftLinesT WHOLE) + 16 bytes: the next body's header, written behind
-// an output's end at row byte <= 192, may run 16 bytes past the last row
-constexpr u32 SEAL_SHIFT_LDS_BYTES = WAVES * SHIFT_LDS_BYTES + 16u;
-// EmitShiftLinesT keeps its flag bits 28..31 (tag_whole, ext_end, ext_start, tag slot) above the
-// output's end d + total in `te`, so the launchers send an output to ST_SHIFT only when
-// d + total < 2^28 with d < 128: total <= SHIFT_TOTAL_MAX.
-constexpr u32 SHIFT_TE_FLAG_BITS = 0xf0000000u;
-constexpr u32 SHIFT_TOTAL_MAX = (1u << 28) - 128u;
-static_assert(((SHIFT_TOTAL_MAX + 127u) & SHIFT_TE_FLAG_BITS) == 0u, "te's end field overlaps its flag bits");
 // UNI (uniform batches: output i at out + i * stride): every lane fetches, once per frame, the
 // workgroup-relative frame index of the 8 outputs it stores for (ds_bpermute) and keeps their
 // 128-byte line offsets from the workgroup's line-aligned base in 8 VGPRs, so the interior-line
@@ -2521,8 +2506,6 @@ __device__ __forceinline__ void combine_tag(const u32 *__restrict__ R0, u32 nseg
 
 // ---- kernels -------------------------------------------------------------
 
-enum Staging { ST_DIRECT = 0, ST_LINES = 1, ST_REGION = 2, ST_SHIFT = 3 };
-
 // Uniform batch of one connection direction: frame i = in[i*in_stride .. +len)
 // -> slot out[i*out_stride .. +out_stride), nonce counter0 + i, flags8[i] (or 0).
 // ST_LINES / ST_REGION need the launcher's preconditions (see czk_seal_uniform);
@@ -2774,13 +2757,8 @@ __global__ __launch_bounds__(BLOCK) CZ_OCC CZ_OPEN_UNI_OCC void k_seal_fanout(
                                (blockIdx.x * BLOCK + threadIdx.x) & ~63u, true, (64u * (u32)out_stride) >> 4);
 }
 
-// The output-ownership rule of a uniform batch and of a fan-out run (header sections 3 and 3c), by
-// the stride alone: whichever emitter the alignments and the length select, the slots of such a
-// batch are written whole.  (2^25: EmitLines' 32-bit offsets; a larger slot is not worth zeroing.)
-__host__ __device__ __forceinline__ bool fanout_owns(uint64_t out_stride)
-{
-    return (out_stride % 128 == 0 && out_stride < (1ull << 25)) || (out_stride % 16 == 0 && 64 * out_stride <= REGION_MAX);
-}
+// The output-ownership rule of a uniform batch and of a fan-out run (czd::owns_slots), for the kernels
+__host__ __device__ __forceinline__ bool fanout_owns(uint64_t out_stride) { return owns_slots(out_stride); }
 
 #if CZ_KPART_HAS(1) || CZ_KPART_HAS(2)
 // Zero bytes [from, stride) of `count` output slots: what a uniform batch that owns its slots owes
@@ -2812,14 +2790,12 @@ __global__ __launch_bounds__(BLOCK) void k_zero_pad(uint8_t *__restrict__ out, u
     }
 }
 
-// after a uniform kernel that wrote bytes [0, done) of every slot (and whatever zeros its emitter adds)
-static void zero_pad_launch(void *out, uint64_t stride, uint32_t count, uint32_t done, hipStream_t s)
+// after a uniform kernel whose plan leaves bytes [l.pad_from, stride) of every slot to be zeroed
+static void zero_pad_launch(const Launch &l, void *out, uint64_t stride, uint32_t count, hipStream_t s)
 {
-    if (count == 0 || stride <= done || !fanout_owns(stride))
-        return;
-    const uint64_t total = ((stride - done + 4095u) / 4096u) * count;
-    hipLaunchKernelGGL(k_zero_pad, dim3((unsigned)(total < (1u << 18) ? total : (1u << 18))), dim3(BLOCK), 0, s,
-                       (uint8_t *)out, stride, count, done);
+    if (l.pad_from != PAD_NONE)
+        hipLaunchKernelGGL(k_zero_pad, dim3(pad_grid(stride, count, l.pad_from)), dim3(BLOCK), 0, s, (uint8_t *)out,
+                           stride, count, (uint32_t)l.pad_from);
 }
 #endif
 
@@ -2847,7 +2823,7 @@ __global__ __launch_bounds__(BLOCK) CZ_OCC CZ_OPEN_UNI_OCC void k_seal_fanout_ru
     uint8_t *o = out + r.out_off;
     bool staged = r.count >= 64u && ((((uintptr_t)payload | (uintptr_t)o | r.out_stride) & 15u) == 0);
     if constexpr (ST == ST_LINES)
-        staged = staged && r.out_stride % 128 == 0 && r.len + 33u >= 256u && r.out_stride < (1ull << 25);
+        staged = staged && r.out_stride % 128 == 0 && r.len + 33u >= LINES_BYTES_MIN && r.out_stride < LINES_STRIDE_MAX;
     else if constexpr (ST == ST_REGION)
         staged = staged && 64 * r.out_stride <= REGION_MAX && ((64 * r.out_stride) >> 4) <= region_part16;
     seal_fanout_wave<ST, PAIR>(payload, r.len, r.flags, subs + r.first_sub, subkeys, o, r.out_stride, r.count,
@@ -3106,8 +3082,7 @@ __global__ __launch_bounds__(BLOCK) CZ_OPEN_CARRY_OCC void k_open_uniform_carry(
 
 #if CZ_KPART_HAS(3)
 // ---- segmented (ragged) batches ------------------------------------------
-constexpr int SEGMODE_LINES = 1;  // line-staged stores for waves of equal-length segments
-constexpr int SEGMODE_PAIR = 2;   // whole-line input loads (seal)
+// (the mode word's bits, SEGMODE_*: cz_dispatch.h)
 
 // A wave takes the line emitter when all 64 lanes hold segments with the same
 // chunk count and 16-byte aligned input/output; otherwise each lane stores directly.
@@ -3133,10 +3108,6 @@ __device__ __forceinline__ bool wave_lines_ok(bool full_wave, u32 nchunks, bool 
         return false;
     return wave_uniform(nchunks) && __builtin_amdgcn_ballot_w64(!al) == 0;
 }
-
-constexpr int SEGMODE_REST = 4;   // k_seal_segments: only the waves k_seal_segments_lines leaves
-constexpr int SEGMODE_SHIFT16 = 8;  // 16-byte aligned outputs not all on 128-byte lines: EmitShiftLines
-constexpr int SEGMODE_ANYIN = 16;   // inputs at any byte offset on the line paths (dword-aligned loads)
 
 // Segment kernels.  With line staging and whole-line loads enabled the launcher runs two
 // kernels over the same segment list: k_seal_segments_lines takes every full wave of aligned
@@ -3816,60 +3787,28 @@ __global__ __launch_bounds__(BLOCK) void k_copy16(uint4 *__restrict__ dst, const
 
 #endif  // CZ_KPART_HAS(3)
 
-// Staging choice for a uniform batch (all pointers 16-byte aligned assumed by the caller check).
-int pick_staging(uint64_t stride, uint32_t out_bytes, bool aligned)
-{
-    if (!aligned)
-        return ST_DIRECT;
-    // (EmitLines' buffer-store offsets, up to 64 * stride, stay below 2^31)
-    if (stride % 128 == 0 && out_bytes >= 256 && stride < (1ull << 25))
-        return ST_LINES;
-    if (stride % 16 == 0 && 64 * stride <= REGION_MAX)
-        return ST_REGION;
-    return ST_DIRECT;
-}
-
 }  // namespace
 
-// run-time tuning knobs (one definition, in part 3; hidden: not part of the library's ABI)
-namespace czk_knobs {
-#define CZ_KNOB __attribute__((visibility("hidden")))
+// run-time tuning knobs (czd::Knobs; one object, defined in part 3; hidden: not part of the library's ABI)
+extern __attribute__((visibility("hidden"))) Knobs g_knobs;
 #if CZ_KPART_HAS(3)
-// g_pair: whole-line input loads for the uniform kernels
-CZ_KNOB int g_pair = 1;
-CZ_KNOB int g_un0 = 1;  // scalar first Salsa round when the high nonce word is wave-uniform
-CZ_KNOB int g_seglines = 1;  // line-staged stores for waves of equal-length segments
-CZ_KNOB int g_shift = 1;     // uniform seal: shifted line staging for bodies at any byte offset
-CZ_KNOB int g_open_ina = 1;  // uniform open: line path for bodies off 16-byte alignment (dword-aligned loads)
-CZ_KNOB int g_seal_ina = 1;  // seal: staged / line paths for payloads off 16-byte alignment
-#ifndef CZ_OPEN_CARRY_DEFAULT
-#define CZ_OPEN_CARRY_DEFAULT 1
+Knobs g_knobs;
 #endif
-CZ_KNOB int g_open_carry = CZ_OPEN_CARRY_DEFAULT;  // uniform open off 16-byte alignment: phase-sorted waves, carried lines
-// segment kernels: waves of 16-byte aligned outputs that are not all on 128-byte lines go through
-// EmitShiftLines (whole cache lines) instead of EmitSegLines (128-byte groups at each output's
-// base, two partial cache lines per group): Zipf seal with 16-byte output slots 1250 -> 1629 GiB/s
-#ifndef CZ_SHIFT16_DEFAULT
-#define CZ_SHIFT16_DEFAULT 1
-#endif
-CZ_KNOB int g_shift16 = CZ_SHIFT16_DEFAULT;
-#else
-extern CZ_KNOB int g_pair;
-extern CZ_KNOB int g_un0;
-extern CZ_KNOB int g_seglines;
-extern CZ_KNOB int g_shift;
-extern CZ_KNOB int g_open_ina;
-extern CZ_KNOB int g_seal_ina;
-extern CZ_KNOB int g_open_carry;
-extern CZ_KNOB int g_shift16;
-#endif
-}  // namespace czk_knobs
-using namespace czk_knobs;
 
 // ---------------------------------------------------------------------------
 // Launchers (called from cz_host.cpp).  No allocation, no synchronisation:
 // safe to capture in a hipGraph.
 // ---------------------------------------------------------------------------
+// Every uniform and fan-out launcher is three steps: the plan (cz_dispatch.h: which instantiation,
+// grid, LDS bytes, zero-pad launch), one switch from the plan's (ST, PAIR, INA) to the instantiation
+// -- a template argument has to be spelled -- and zero_pad_launch.  A plan outside a launcher's
+// instantiations is an error, never another kernel.  The order of the cases is the order in which the
+// compiler emits the instantiations into the code object (the ST_SHIFT kernels call an outlined
+// function PC-relative), so reordering them changes those kernels' machine code, not what they do.
+#define CZ_INST(ST, PR, INA) ((int)(ST) | ((PR) ? 4 : 0) | ((INA) << 3))
+#define CZ_INST_OF(l) CZ_INST((l).st, (l).pair, (l).ina)
+#define CZ_LAUNCH(...) hipLaunchKernelGGL(__VA_ARGS__)  // (expands an argument-list macro first)
+
 extern "C" {
 
 #if CZ_KPART_HAS(1)
@@ -3879,161 +3818,100 @@ hipError_t czk_seal_uniform(const void *in, uint64_t in_stride, void *out, uint6
 {
     if (count == 0)
         return hipSuccess;
-    dim3 grid((count + BLOCK - 1) / BLOCK);
-    const bool in_al = ((((uintptr_t)in | in_stride) & 15u) == 0);
-    const bool al = in_al && ((((uintptr_t)out | out_stride) & 15u) == 0);
-#define CZ_SEAL_LAUNCH(ST, PR, LDS)                                                                        \
-    hipLaunchKernelGGL((k_seal_uniform<ST, PR>), grid, dim3(BLOCK), (LDS), s, (const uint8_t *)in, in_stride,   \
-                       (uint8_t *)out, out_stride, count, len, (const uint8_t *)subkey, counter0, flags8, g_un0)
-    // payloads off 16-byte alignment (messages packed back to back): the staged kernels with
-    // dword-aligned loads (INA 8 / 1) instead of lane-wise unaligned loads and byte-exact stores
-    if (!in_al && g_pair && g_seal_ina && len >= 64u) {
-        const bool out_al = ((((uintptr_t)out | out_stride) & 15u) == 0);
-        int so = pick_staging(out_stride, len + 33u, out_al);
-        if (so == ST_DIRECT && len + 33u >= 256u && out_stride < (1ull << 22) && len <= SHIFT_TOTAL_MAX - 33u && g_shift)
-            so = ST_SHIFT;
-        const bool i8 = (((uintptr_t)in | in_stride) & 7u) == 0;
-#define CZ_SEAL_LAUNCH_INA(ST, PR, INA, LDS)                                                                  \
-    hipLaunchKernelGGL((k_seal_uniform_ina<ST, PR, INA>), grid, dim3(BLOCK), (LDS), s, (const uint8_t *)in,        \
-                       in_stride, (uint8_t *)out, out_stride, count, len, (const uint8_t *)subkey, counter0,       \
-                       flags8, g_un0)
-        const unsigned lds_l = WAVES * (LINE_LDS_BYTES + HOLD_LDS_BYTES), lds_s = SEAL_SHIFT_LDS_BYTES;
-        const unsigned lds_r = (unsigned)(WAVES * 64 * out_stride);
-        if (so == ST_LINES) {
-            if (i8) CZ_SEAL_LAUNCH_INA(ST_LINES, true, 8, lds_l);
-            else CZ_SEAL_LAUNCH_INA(ST_LINES, true, 1, lds_l);
-            zero_pad_launch(out, out_stride, count, (len + 33u + 127u) & ~127u, s);
-            return hipGetLastError();
-        }
-        if (so == ST_SHIFT) {
-            if (i8) CZ_SEAL_LAUNCH_INA(ST_SHIFT, true, 8, lds_s);
-            else CZ_SEAL_LAUNCH_INA(ST_SHIFT, true, 1, lds_s);
-            zero_pad_launch(out, out_stride, count, len + 33u, s);
-            return hipGetLastError();
-        }
-        if (so == ST_REGION) {
-            if (i8) CZ_SEAL_LAUNCH_INA(ST_REGION, false, 8, lds_r);
-            else CZ_SEAL_LAUNCH_INA(ST_REGION, false, 1, lds_r);
-            return hipGetLastError();
-        }
-#undef CZ_SEAL_LAUNCH_INA
+    const Launch l = plan_seal_uniform((uintptr_t)in, in_stride, (uintptr_t)out, out_stride, count, len, g_knobs);
+#define CZ_SEAL_ARGS                                                                                              \
+    dim3(l.grid), dim3(BLOCK), l.lds, s, (const uint8_t *)in, in_stride, (uint8_t *)out, out_stride, count, len, \
+        (const uint8_t *)subkey, counter0, flags8, g_knobs.un0
+#define CZ_CASE(ST, PR) \
+    case CZ_INST(ST, PR, 16): CZ_LAUNCH((k_seal_uniform<ST, PR>), CZ_SEAL_ARGS); break;
+#define CZ_CASE_INA(ST, PR, INA) \
+    case CZ_INST(ST, PR, INA): CZ_LAUNCH((k_seal_uniform_ina<ST, PR, INA>), CZ_SEAL_ARGS); break;
+    switch (CZ_INST_OF(l)) {
+        CZ_CASE_INA(ST_LINES, true, 8) CZ_CASE_INA(ST_LINES, true, 1) CZ_CASE_INA(ST_SHIFT, true, 8) CZ_CASE_INA(ST_SHIFT, true, 1)
+        CZ_CASE_INA(ST_REGION, false, 8) CZ_CASE_INA(ST_REGION, false, 1)
+        CZ_CASE(ST_LINES, true) CZ_CASE(ST_SHIFT, true) CZ_CASE(ST_DIRECT, true)
+        CZ_CASE(ST_LINES, false) CZ_CASE(ST_REGION, false) CZ_CASE(ST_SHIFT, false) CZ_CASE(ST_DIRECT, false)
+    default: return hipErrorInvalidValue;
     }
-    int st = pick_staging(out_stride, len + 33u, al);
-    // bodies at any byte offset (dense slots, wire layout) from aligned payloads: shifted line staging
-    // (EmitShiftLinesUni's buffer-store offsets, below 256 * stride + len + 160, stay below 2^31)
-    if (st == ST_DIRECT && in_al && len + 33u >= 256u && out_stride < (1ull << 22) && len <= SHIFT_TOTAL_MAX - 33u && g_shift)
-        st = ST_SHIFT;
-    const unsigned lds = st == ST_LINES ? WAVES * (LINE_LDS_BYTES + HOLD_LDS_BYTES)
-                                        : st == ST_SHIFT ? SEAL_SHIFT_LDS_BYTES
-                                        : (st == ST_REGION ? (unsigned)(WAVES * 64 * out_stride) : 0u);
-    // whole-line input pays for large frames (A/B: 4 KiB seal 2.34 vs 2.51 ms) but
-    // not for the small frames of the region stager (100 B: 0.119 vs 0.114 ms)
-    if (g_pair && st != ST_REGION) {
-        if (st == ST_LINES) CZ_SEAL_LAUNCH(ST_LINES, true, lds);
-        else if (st == ST_SHIFT) CZ_SEAL_LAUNCH(ST_SHIFT, true, lds);
-        else CZ_SEAL_LAUNCH(ST_DIRECT, true, 0);
-    } else {
-        if (st == ST_LINES) CZ_SEAL_LAUNCH(ST_LINES, false, lds);
-        else if (st == ST_REGION) CZ_SEAL_LAUNCH(ST_REGION, false, lds);
-        else if (st == ST_SHIFT) CZ_SEAL_LAUNCH(ST_SHIFT, false, lds);
-        else CZ_SEAL_LAUNCH(ST_DIRECT, false, 0);
-    }
-#undef CZ_SEAL_LAUNCH
-    // the rest of owned slots (header section 3): nothing for the region emitter, which writes whole
-    // slots, nor for line-staged slots that end with the body's last line
-    if (st != ST_REGION)
-        zero_pad_launch(out, out_stride, count, st == ST_LINES ? (len + 33u + 127u) & ~127u : len + 33u, s);
+#undef CZ_CASE_INA
+#undef CZ_CASE
+    zero_pad_launch(l, out, out_stride, count, s);
     return hipGetLastError();
 }
 
-// 1 when a uniform batch with this out_stride owns its whole slots (the host-staged paths zero the
-// slots themselves when it does not).  Host code, no device call.
-int czk_owns_slots(uint64_t out_stride) { return fanout_owns(out_stride) ? 1 : 0; }
+int czk_owns_slots(uint64_t out_stride) { return owns_slots(out_stride) ? 1 : 0; }
 
-// Box-layout input (MODE_BOX): whole-line staging for 128-byte multiple output slots, direct
-// stores otherwise; whole-line input loads always (the box is read where it lies).
 hipError_t czk_seal_uniform_box(const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint32_t count,
                                 uint32_t len, const void *subkey, uint64_t counter0, hipStream_t s)
 {
     if (count == 0)
         return hipSuccess;
-    dim3 grid((count + BLOCK - 1) / BLOCK);
-    const bool al = ((((uintptr_t)in | in_stride | (uintptr_t)out | out_stride) & 15u) == 0);
-    const int st = pick_staging(out_stride, len + 33u, al);
-    if (st == ST_LINES)
-        hipLaunchKernelGGL((k_seal_uniform<ST_LINES, true, MODE_BOX>), grid, dim3(BLOCK),
-                           WAVES * (LINE_LDS_BYTES + HOLD_LDS_BYTES), s, (const uint8_t *)in, in_stride, (uint8_t *)out,
-                           out_stride, count, len, (const uint8_t *)subkey, counter0, nullptr, g_un0);
-    else
-        hipLaunchKernelGGL((k_seal_uniform<ST_DIRECT, true, MODE_BOX>), grid, dim3(BLOCK), 0, s, (const uint8_t *)in,
-                           in_stride, (uint8_t *)out, out_stride, count, len, (const uint8_t *)subkey, counter0, nullptr,
-                           g_un0);
-    zero_pad_launch(out, out_stride, count, st == ST_LINES ? (len + 33u + 127u) & ~127u : len + 33u, s);
+    const Launch l = plan_seal_box((uintptr_t)in, in_stride, (uintptr_t)out, out_stride, count, len, g_knobs);
+    const uint8_t *flags8 = nullptr;
+#define CZ_CASE(ST) \
+    case ST: CZ_LAUNCH((k_seal_uniform<ST, true, MODE_BOX>), CZ_SEAL_ARGS); break;
+    switch (l.st) {
+        CZ_CASE(ST_LINES) CZ_CASE(ST_DIRECT)
+    default: return hipErrorInvalidValue;
+    }
+#undef CZ_CASE
+#undef CZ_SEAL_ARGS
+    zero_pad_launch(l, out, out_stride, count, s);
     return hipGetLastError();
 }
 
-// PUB fan-out: `count` seals of one payload (k_seal_fanout).  The batch owns whole slots when
-// out_stride is a multiple of 128 (below 32 MiB: EmitLines' buffer-store offsets, up to
-// 64 * stride, stay below 2^31) or a multiple of 16 with 64 slots in REGION_MAX bytes, whatever the
-// base alignments: the staged emitters write the zeros past a body with its lines, the lane-wise
-// path (partial waves, a base or payload off 16-byte alignment) writes them itself.
+// k_seal_fanout / k_seal_fanout_runs K for the plan l: whole-line input loads except for the region stager
+#define CZ_CASE(K, ST, PR, l, ...) \
+    case CZ_INST(ST, PR, 16): CZ_LAUNCH((K<ST, PR>), dim3((l).grid), dim3(BLOCK), (l).lds, s, __VA_ARGS__); break;
+#define CZ_FANOUT_SWITCH(K, l, ...)                                                                          \
+    switch (CZ_INST_OF(l)) {                                                                                 \
+        CZ_CASE(K, ST_LINES, true, l, __VA_ARGS__) CZ_CASE(K, ST_REGION, false, l, __VA_ARGS__)              \
+        CZ_CASE(K, ST_DIRECT, true, l, __VA_ARGS__)                                                          \
+    default: return hipErrorInvalidValue;                                                                    \
+    }
+
+// PUB fan-out: `count` seals of one payload (k_seal_fanout).  The batch owns whole slots by its
+// stride alone (owns_slots), whatever the base alignments: the staged emitters write the zeros past
+// a body with its lines, the lane-wise path (partial waves, a base or payload off 16-byte
+// alignment) writes them itself.
 hipError_t czk_seal_fanout(const void *payload, uint32_t len, uint32_t flags, const cz_fanout_sub *subs,
                            const void *subkeys, void *out, uint64_t out_stride, uint32_t count, hipStream_t s)
 {
     if (count == 0)
         return hipSuccess;
-    dim3 grid((count + BLOCK - 1) / BLOCK);
-    const bool owns = fanout_owns(out_stride);
-    const bool al = ((((uintptr_t)payload | (uintptr_t)out | out_stride) & 15u) == 0);
-    const int st = count >= 64u ? pick_staging(out_stride, len + 33u, al) : ST_DIRECT;
-#define CZ_FANOUT_LAUNCH(ST, PR, LDS)                                                                          \
-    hipLaunchKernelGGL((k_seal_fanout<ST, PR>), grid, dim3(BLOCK), (LDS), s, (const uint8_t *)payload, len, flags, \
-                       subs, (const uint8_t *)subkeys, (uint8_t *)out, out_stride, count, owns ? 1 : 0)
-    // whole-line input loads as czk_seal_uniform: not for the small frames of the region stager
-    if (st == ST_LINES)
-        CZ_FANOUT_LAUNCH(ST_LINES, true, WAVES * (LINE_LDS_BYTES + HOLD_LDS_BYTES));
-    else if (st == ST_REGION)
-        CZ_FANOUT_LAUNCH(ST_REGION, false, (unsigned)(WAVES * 64 * out_stride));
-    else
-        CZ_FANOUT_LAUNCH(ST_DIRECT, true, 0);
-#undef CZ_FANOUT_LAUNCH
+    const Launch l = plan_fanout(out_stride, len, count, aligned16((uintptr_t)payload | (uintptr_t)out | out_stride));
+    CZ_FANOUT_SWITCH(k_seal_fanout, l, (const uint8_t *)payload, len, flags, subs, (const uint8_t *)subkeys,
+                     (uint8_t *)out, out_stride, count, owns_slots(out_stride) ? 1 : 0)
     return hipGetLastError();
 }
 
-// The staging class cz_plan_fanout gives the full waves of a run (CZ_FANOUT_LINES / _REGION /
-// _DIRECT): czk_seal_fanout's choice for that run alone.  Host code, no device call.
 int czk_fanout_class(uint64_t out_stride, uint32_t len, uint32_t count, int aligned)
 {
-    const int st = count >= 64u ? pick_staging(out_stride, len + 33u, aligned != 0) : (int)ST_DIRECT;
-    return st == ST_LINES ? CZ_FANOUT_LINES : (st == ST_REGION ? CZ_FANOUT_REGION : CZ_FANOUT_DIRECT);
+    return plan_fanout_class(out_stride, len, count, aligned != 0);
 }
 
 // Grouped PUB fan-out (k_seal_fanout_runs): the wave table holds class_count[CZ_FANOUT_LINES] waves
 // for the line emitter, then class_count[CZ_FANOUT_REGION] for the region emitter, then
 // class_count[CZ_FANOUT_DIRECT] lane-wise ones -- at most three launches whatever the number of
-// runs.  region_stride: the largest out_stride of the region slice (0 or above REGION_MAX / 64:
-// REGION_MAX / 64); every wave of that launch gets an LDS partition of 64 such slots.
+// runs.  region_stride: the largest out_stride of the region slice (fanout_region_part16).
 hipError_t czk_seal_fanout_runs(const cz_fanout_run *runs, const cz_fanout_wave *waves, const uint32_t class_count[3],
                                 uint32_t region_stride, const void *in, const cz_fanout_sub *subs,
                                 const void *subkeys, void *out, hipStream_t s)
 {
-    if (region_stride == 0 || region_stride > REGION_MAX / 64)
-        region_stride = REGION_MAX / 64;
-    const u32 part16 = (64u * ((region_stride + 15u) & ~15u)) >> 4;
-#define CZ_FANOUT_RUNS_LAUNCH(ST, PR, LDS, W0, NW)                                                             \
-    hipLaunchKernelGGL((k_seal_fanout_runs<ST, PR>), dim3(((NW) + WAVES - 1) / WAVES), dim3(BLOCK), (LDS), s, runs, \
-                       waves + (W0), (NW), (const uint8_t *)in, subs, (const uint8_t *)subkeys, (uint8_t *)out, part16)
-    const uint32_t nl = class_count[CZ_FANOUT_LINES], nr = class_count[CZ_FANOUT_REGION],
-                   nd = class_count[CZ_FANOUT_DIRECT];
-    if (nl)
-        CZ_FANOUT_RUNS_LAUNCH(ST_LINES, true, WAVES * (LINE_LDS_BYTES + HOLD_LDS_BYTES), 0, nl);
-    if (nr)
-        CZ_FANOUT_RUNS_LAUNCH(ST_REGION, false, (unsigned)(WAVES * 16u * part16), nl, nr);
-    if (nd)
-        CZ_FANOUT_RUNS_LAUNCH(ST_DIRECT, true, 0, nl + nr, nd);
-#undef CZ_FANOUT_RUNS_LAUNCH
+    static_assert(CZ_FANOUT_LINES == 0 && CZ_FANOUT_REGION == 1 && CZ_FANOUT_DIRECT == 2, "classes in table order");
+    const u32 part16 = fanout_region_part16(region_stride);
+    uint32_t w0 = 0;
+    for (int cls = 0; cls < 3; w0 += class_count[cls++]) {
+        if (class_count[cls] == 0)
+            continue;
+        const Launch l = plan_fanout_runs(cls, class_count[cls], part16);
+        CZ_FANOUT_SWITCH(k_seal_fanout_runs, l, runs, waves + w0, class_count[cls], (const uint8_t *)in, subs,
+                         (const uint8_t *)subkeys, (uint8_t *)out, part16)
+    }
     return hipGetLastError();
 }
+#undef CZ_FANOUT_SWITCH
+#undef CZ_CASE
 
 #ifdef CZ_DIAG_CLOCK
 // diagnostic builds only: copy the last k_seal_uniform launch's wave stamps (4 x u64 per wave) out
@@ -4075,125 +3953,58 @@ hipError_t czk_open_desc(const cz_frame_desc *desc, const uint32_t *order, uint3
 #endif  // CZ_KPART_HAS(3)
 
 #if CZ_KPART_HAS(2)
+// One launch of an open plan.  `n`: the frames, for k_open_uniform_carry the waves (of period P);
+// tail: the frames behind a carried head (plan_open_uniform).
+static hipError_t open_uniform_launch(const Launch &l, const uint8_t *in, uint64_t in_stride, uint8_t *out,
+                                      uint64_t out_stride, uint32_t n, uint32_t P, uint32_t size, const uint8_t *subkey,
+                                      uint64_t floor0, int check, uint16_t *status, int tail, hipStream_t s)
+{
+    const bool carry = l.family == K_OPEN_UNIFORM_CARRY;
+#define CZ_CASE(ST, PR, INA)                                                                                          \
+    case CZ_INST(ST, PR, INA):                                                                                        \
+        CZ_LAUNCH((k_open_uniform<ST, PR, INA>), dim3(l.grid), dim3(BLOCK), l.lds, s, in, in_stride, out, out_stride, \
+                  n, size, subkey, floor0, check, status, g_knobs.un0, tail);                                         \
+        break;
+#define CZ_CASE_CARRY(INA)                                                                                          \
+    case CZ_INST(ST_LINES, true, INA) | 1024:                                                                       \
+        CZ_LAUNCH((k_open_uniform_carry<INA>), dim3(l.grid), dim3(BLOCK), l.lds, s, in, in_stride, out, out_stride, \
+                  n, P, size, subkey, floor0, check, status, g_knobs.un0);                                          \
+        break;
+    switch (CZ_INST_OF(l) | (carry ? 1024 : 0)) {
+        CZ_CASE(ST_REGION, false, 8) CZ_CASE(ST_REGION, false, 1)
+        CZ_CASE_CARRY(8) CZ_CASE_CARRY(1)
+        CZ_CASE(ST_LINES, true, 8) CZ_CASE(ST_LINES, true, 1)
+        CZ_CASE(ST_SHIFT, true, 16) CZ_CASE(ST_SHIFT, true, 8) CZ_CASE(ST_SHIFT, true, 1)
+        CZ_CASE(ST_LINES, true, 16) CZ_CASE(ST_DIRECT, true, 16)
+        CZ_CASE(ST_LINES, false, 16) CZ_CASE(ST_REGION, false, 16) CZ_CASE(ST_DIRECT, false, 16)
+    default: return hipErrorInvalidValue;
+    }
+#undef CZ_CASE_CARRY
+#undef CZ_CASE
+    return hipSuccess;
+}
+
 hipError_t czk_open_uniform(const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint32_t count,
                             uint32_t size, const void *subkey, uint64_t floor0, int check, uint16_t *status,
                             hipStream_t s)
 {
     if (count == 0)
         return hipSuccess;
-    dim3 grid((count + BLOCK - 1) / BLOCK);
-    const bool al = ((((uintptr_t)in | (uintptr_t)out | in_stride | out_stride) & 15u) == 0);
-    const uint32_t nout = size >= 33u ? size - 33u : 0u;
-#define CZ_OPEN_LAUNCH(ST, PR, LDS)                                                                        \
-    hipLaunchKernelGGL((k_open_uniform<ST, PR>), grid, dim3(BLOCK), (LDS), s, (const uint8_t *)in, in_stride,   \
-                       (uint8_t *)out, out_stride, count, size, (const uint8_t *)subkey, floor0, check, status, g_un0, 0)
-#define CZ_OPEN_LAUNCH_INA(ST, INA, LDS)                                                                     \
-    hipLaunchKernelGGL((k_open_uniform<ST, true, INA>), grid, dim3(BLOCK), (LDS), s, (const uint8_t *)in,          \
-                       in_stride, (uint8_t *)out, out_stride, count, size, (const uint8_t *)subkey, floor0, check, \
-                       status, g_un0, 0)
-    const int st = size >= 33u ? pick_staging(out_stride, nout, al) : (int)ST_DIRECT;
-    const unsigned lds = st == ST_LINES ? WAVES * LINE_LDS_BYTES : (st == ST_REGION ? (unsigned)(WAVES * 64 * out_stride) : 0u);
-    // bodies off 16-byte alignment (the dense wire layout) into line-aligned plaintext slots: the
-    // line path with dword-aligned loads (INA 8 / 1) instead of lane-wise byte-exact stores
-    const bool out_al = ((((uintptr_t)out | out_stride) & 15u) == 0);
-    int st_out = size >= 33u ? pick_staging(out_stride, nout, out_al) : (int)ST_DIRECT;
-    // plaintext at any byte offset (slots that are not 128-byte multiples): byte-shifted line
-    // staging, as the seal's bodies (EmitShiftLinesUni; its buffer-store offsets stay below 2^31)
-    if (st_out == ST_DIRECT && size >= 33u && nout >= 256u && nout <= SHIFT_TOTAL_MAX && out_stride < (1ull << 22) &&
-        g_shift)
-        st_out = ST_SHIFT;
-    const uint64_t ia = (uintptr_t)in | in_stride;
-    const int ina = (ia & 15u) == 0 ? 16 : (ia & 7u) == 0 ? 8 : 1;
-    const unsigned lds_out_region = (unsigned)(WAVES * 64 * out_stride);
-    if (ina != 16 && st_out == ST_REGION && g_open_ina) {
-        // small bodies (64 plaintext slots <= 16 KiB) off 16-byte alignment: region staging
-        if (ina == 8)
-            hipLaunchKernelGGL((k_open_uniform<ST_REGION, false, 8>), grid, dim3(BLOCK), lds_out_region, s,
-                               (const uint8_t *)in, in_stride, (uint8_t *)out, out_stride, count, size,
-                               (const uint8_t *)subkey, floor0, check, status, g_un0, 0);
-        else
-            hipLaunchKernelGGL((k_open_uniform<ST_REGION, false, 1>), grid, dim3(BLOCK), lds_out_region, s,
-                               (const uint8_t *)in, in_stride, (uint8_t *)out, out_stride, count, size,
-                               (const uint8_t *)subkey, floor0, check, status, g_un0, 0);
-        return hipGetLastError();
+    const OpenLaunch p = plan_open_uniform((uintptr_t)in, in_stride, (uintptr_t)out, out_stride, count, size, g_knobs);
+    const uint8_t *bin = (const uint8_t *)in, *key = (const uint8_t *)subkey;
+    uint8_t *bout = (uint8_t *)out;
+    hipError_t e = open_uniform_launch(p.head, bin, in_stride, bout, out_stride, p.nwaves ? p.nwaves : count, p.P, size, key,
+                                       floor0, check, status, 0, s);
+    if (e != hipSuccess)
+        return e;
+    zero_pad_launch(p.head, out, out_stride, count, s);
+    if (p.done && p.done < count) {  // the frames behind a carried head
+        if ((e = hipGetLastError()) != hipSuccess ||
+            (e = open_uniform_launch(p.tail, bin + p.done * in_stride, in_stride, bout + p.done * out_stride, out_stride,
+                                     count - (uint32_t)p.done, 0, size, key, floor0, check, status + p.done, 1, s)) !=
+                hipSuccess)
+            return e;
     }
-    // (INA 1 -- any byte offset -- measured 1.3% slower with carried lines at 2 waves per SIMD than
-    // the straddling loads at 3, so only 8-byte aligned bodies take it: +2.6%)
-    // (cz_tune("open_carry", 2): INA 1 too, A/B only)
-    if (g_pair && st_out == ST_LINES && (ina == 8 || (ina == 1 && g_open_carry == 2)) && g_open_ina && g_open_carry &&
-        nout >= 256u) {
-        // phase-sorted waves with carried aligned lines (k_open_uniform_carry): whole blocks of 64 P
-        // frames, P = the period of the bodies' line phase; the rest through k_open_uniform
-        uint64_t g = in_stride & 127u, m = 128u;
-        while (g) {  // gcd(in_stride mod 128, 128)
-            const uint64_t t = m % g;
-            m = g;
-            g = t;
-        }
-        const uint32_t P = (uint32_t)(128u / m);
-        const uint64_t blocks = count / (64ull * P);
-        if (blocks > 0 && 64ull * P * out_stride < (1ull << 31)) {
-            const uint32_t nwaves = (uint32_t)(blocks * P);
-            const dim3 cgrid((nwaves + WAVES - 1) / WAVES);
-            if (ina == 8)
-                hipLaunchKernelGGL((k_open_uniform_carry<8>), cgrid, dim3(BLOCK), WAVES * LINE_LDS_BYTES, s,
-                                   (const uint8_t *)in, in_stride, (uint8_t *)out, out_stride, nwaves, P, size,
-                                   (const uint8_t *)subkey, floor0, check, status, g_un0);
-            else
-                hipLaunchKernelGGL((k_open_uniform_carry<1>), cgrid, dim3(BLOCK), WAVES * LINE_LDS_BYTES, s,
-                                   (const uint8_t *)in, in_stride, (uint8_t *)out, out_stride, nwaves, P, size,
-                                   (const uint8_t *)subkey, floor0, check, status, g_un0);
-            zero_pad_launch(out, out_stride, count, (nout + 127u) & ~127u, s);
-            const uint64_t done = blocks * 64ull * P;
-            if (done < count) {
-                hipError_t e = hipGetLastError();
-                if (e != hipSuccess)
-                    return e;
-                const uint32_t rest = count - (uint32_t)done;
-                const dim3 tgrid((rest + BLOCK - 1) / BLOCK);
-                const uint8_t *tin = (const uint8_t *)in + done * in_stride;
-                uint8_t *tout = (uint8_t *)out + done * out_stride;
-                if (ina == 8)
-                    hipLaunchKernelGGL((k_open_uniform<ST_LINES, true, 8>), tgrid, dim3(BLOCK), WAVES * LINE_LDS_BYTES,
-                                       s, tin, in_stride, tout, out_stride, rest, size, (const uint8_t *)subkey, floor0,
-                                       check, status + done, g_un0, 1);
-                else
-                    hipLaunchKernelGGL((k_open_uniform<ST_LINES, true, 1>), tgrid, dim3(BLOCK), WAVES * LINE_LDS_BYTES,
-                                       s, tin, in_stride, tout, out_stride, rest, size, (const uint8_t *)subkey, floor0,
-                                       check, status + done, g_un0, 1);
-            }
-            return hipGetLastError();
-        }
-    }
-    if (g_pair && (st_out == ST_SHIFT || (st_out == ST_LINES && ina != 16)) && (ina == 16 || g_open_ina)) {
-        if (st_out == ST_LINES) {
-            if (ina == 8)
-                CZ_OPEN_LAUNCH_INA(ST_LINES, 8, WAVES * LINE_LDS_BYTES);
-            else
-                CZ_OPEN_LAUNCH_INA(ST_LINES, 1, WAVES * LINE_LDS_BYTES);
-        } else if (ina == 16) {
-            CZ_OPEN_LAUNCH_INA(ST_SHIFT, 16, WAVES * SHIFT_LDS_BYTES);
-        } else if (ina == 8) {
-            CZ_OPEN_LAUNCH_INA(ST_SHIFT, 8, WAVES * SHIFT_LDS_BYTES);
-        } else {
-            CZ_OPEN_LAUNCH_INA(ST_SHIFT, 1, WAVES * SHIFT_LDS_BYTES);
-        }
-        zero_pad_launch(out, out_stride, count, st_out == ST_LINES ? (nout + 127u) & ~127u : nout, s);
-        return hipGetLastError();
-    }
-    if (g_pair && st != ST_REGION) {
-        if (st == ST_LINES) CZ_OPEN_LAUNCH(ST_LINES, true, lds);
-        else CZ_OPEN_LAUNCH(ST_DIRECT, true, 0);
-    } else {
-        if (st == ST_LINES) CZ_OPEN_LAUNCH(ST_LINES, false, lds);
-        else if (st == ST_REGION) CZ_OPEN_LAUNCH(ST_REGION, false, lds);
-        else CZ_OPEN_LAUNCH(ST_DIRECT, false, 0);
-    }
-    // the rest of owned slots, as czk_seal_uniform
-    if (st != ST_REGION)
-        zero_pad_launch(out, out_stride, count, st == ST_LINES ? (nout + 127u) & ~127u : nout, s);
-#undef CZ_OPEN_LAUNCH
-#undef CZ_OPEN_LAUNCH_INA
     return hipGetLastError();
 }
 
@@ -4212,8 +4023,6 @@ extern "C" __attribute__((visibility("default"))) int cz_diag_clock_read_open(ui
 #endif  // CZ_KPART_HAS(2)
 
 #if CZ_KPART_HAS(3)
-uint32_t czk_nacl_one_limit(void);
-
 hipError_t czk_nacl_one(void *st, uint32_t len, int open, void *subcache, int miss, uint32_t out_off,
                         const uint8_t k[32], const uint8_t n[24], hipStream_t s)
 {
@@ -4281,18 +4090,15 @@ hipError_t czk_seal_segments(const cz_frame_desc *desc, const cz_segment *segs, 
                              uint32_t ncomb, const void *in, void *out, const void *subkeys, void *work, hipStream_t s)
 {
     const dim3 grid((nseg + BLOCK - 1) / BLOCK);
-    if (nseg && g_seglines && g_pair) {
-        const int mode = SEGMODE_LINES | SEGMODE_PAIR | (g_shift16 ? SEGMODE_SHIFT16 : 0) | (g_seal_ina ? SEGMODE_ANYIN : 0);
+    const int mode = seal_segments_mode(g_knobs);
+    // two passes over the segment list (seal_segments_two_pass): the full waves of aligned segments, then the rest
+    if (nseg && seal_segments_two_pass(g_knobs))
         hipLaunchKernelGGL(k_seal_segments_lines, grid, dim3(BLOCK), WAVES * SHIFT_LDS_BYTES, s, desc, segs, nseg,
                            (const uint8_t *)in, (uint8_t *)out, (const uint8_t *)subkeys, (u32 *)work, mode);
-        hipLaunchKernelGGL(k_seal_segments, grid, dim3(BLOCK), g_seal_ina ? WAVES * SHIFT_LDS_BYTES : 0, s, desc, segs,
-                           nseg, (const uint8_t *)in, (uint8_t *)out, (const uint8_t *)subkeys, (u32 *)work,
-                           mode | SEGMODE_REST);
-    } else if (nseg) {
-        hipLaunchKernelGGL(k_seal_segments, grid, dim3(BLOCK), WAVES * SHIFT_LDS_BYTES, s, desc, segs, nseg,
+    if (nseg)
+        hipLaunchKernelGGL(k_seal_segments, grid, dim3(BLOCK), seal_segments_lds(g_knobs), s, desc, segs, nseg,
                            (const uint8_t *)in, (uint8_t *)out, (const uint8_t *)subkeys, (u32 *)work,
-                           (g_seglines ? SEGMODE_LINES : 0) | (g_pair ? SEGMODE_PAIR : 0));
-    }
+                           mode | (seal_segments_two_pass(g_knobs) ? SEGMODE_REST : 0));
     if (ncomb)
         hipLaunchKernelGGL(k_seal_combine, dim3((ncomb + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, desc, comb, ncomb,
                            (uint8_t *)out, (const u32 *)work);
@@ -4306,9 +4112,7 @@ hipError_t czk_open_segments(const cz_frame_desc *desc, const cz_segment *segs, 
     if (nseg)
         hipLaunchKernelGGL(k_open_segments, dim3((nseg + BLOCK - 1) / BLOCK), dim3(BLOCK), WAVES * SHIFT_LDS_BYTES, s,
                            desc, segs, nseg, (const uint8_t *)in, (uint8_t *)out, (const uint8_t *)subkeys,
-                           (u32 *)work, status, nonces,
-                           (g_seglines ? SEGMODE_LINES : 0) | (g_pair ? SEGMODE_PAIR : 0) | (g_shift16 ? SEGMODE_SHIFT16 : 0) |
-                               (g_open_ina ? SEGMODE_ANYIN : 0));
+                           (u32 *)work, status, nonces, open_segments_mode(g_knobs));
     if (ncomb)
         hipLaunchKernelGGL(k_open_combine, dim3((ncomb + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, desc, comb, ncomb,
                            (const uint8_t *)in, (uint8_t *)out, (const u32 *)work, status);
@@ -4327,48 +4131,16 @@ hipError_t czk_v2_copy(const cz_v2_item *items, uint32_t count, const void *src,
 
 int czk_tune(const char *key, int value)
 {
-    if (!key)
-        return -1;
-    if (key[0] == 'p' && key[1] == 'a' && key[2] == 'i' && key[3] == 'r' && key[4] == 0) {
-        int old = g_pair;
-        g_pair = value != 0;
-        return old;
-    }
-    if (key[0] == 'u' && key[1] == 'n' && key[2] == '0' && key[3] == 0) {
-        int old = g_un0;
-        g_un0 = value != 0;
-        return old;
-    }
-    if (__builtin_strcmp(key, "seglines") == 0) {
-        int old = g_seglines;
-        g_seglines = value != 0;
-        return old;
-    }
-    if (__builtin_strcmp(key, "seal_ina") == 0) {
-        int old = g_seal_ina;
-        g_seal_ina = value != 0;
-        return old;
-    }
-    if (__builtin_strcmp(key, "open_ina") == 0) {
-        int old = g_open_ina;
-        g_open_ina = value != 0;
-        return old;
-    }
-    if (__builtin_strcmp(key, "open_carry") == 0) {
-        int old = g_open_carry;
-        g_open_carry = value < 0 ? 0 : value > 2 ? 2 : value;
-        return old;
-    }
-    if (__builtin_strcmp(key, "shift16") == 0) {
-        int old = g_shift16;
-        g_shift16 = value != 0;
-        return old;
-    }
-    if (__builtin_strcmp(key, "shift") == 0) {
-        int old = g_shift;
-        g_shift = value != 0;
-        return old;
-    }
+    // max 1: on / off (any non-zero value is on); above: clamped to [0, max]
+    static const struct { const char *name; int Knobs::*knob; int max; } table[] = {{"pair", &Knobs::pair, 1},         {"un0", &Knobs::un0, 1},           {"seglines", &Knobs::seglines, 1},
+                 {"shift", &Knobs::shift, 1},       {"open_ina", &Knobs::open_ina, 1}, {"seal_ina", &Knobs::seal_ina, 1},
+                 {"open_carry", &Knobs::open_carry, 2}, {"shift16", &Knobs::shift16, 1}};
+    for (const auto &t : table)
+        if (key && __builtin_strcmp(key, t.name) == 0) {
+            const int old = g_knobs.*t.knob;
+            g_knobs.*t.knob = t.max == 1 ? value != 0 : value < 0 ? 0 : value > t.max ? t.max : value;
+            return old;
+        }
     return -1;
 }
 

@@ -19,15 +19,7 @@ struct cz_session_job {
 };
 static_assert(sizeof(cz_session_job) == 24, "cz_session_job layout");
 
-extern "C" {
-// table[32 * tx_key], table[32 * rx_key] = HSalsa20(cnPrecom, MESSAGE prefix) for jobs[0, count)
-hipError_t czk_session_subkeys(const cz_session_job *d_jobs, uint32_t count, const void *d_base, void *d_table,
-                               hipStream_t s);
-// zero rec_bytes (a multiple of 16) at base + offset + idx[i] * rec_bytes for i in [0, count); base + offset
-// 16-byte aligned
-hipError_t czk_scatter_wipe(void *d_base, const uint32_t *d_idx, uint32_t count, uint32_t rec_bytes, uint64_t offset,
-                            hipStream_t s);
-}
+// (the launchers czk_session_subkeys and czk_scatter_wipe: cz_launch.h)
 
 struct cz_engine;
 
