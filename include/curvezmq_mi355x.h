@@ -305,6 +305,70 @@ int cz_seal_fanout_runs(const cz_fanout_run *d_runs, uint32_t nruns, const cz_fa
                         const uint32_t class_count[3], uint32_t region_stride, const void *d_in,
                         const cz_fanout_sub *d_subs, const void *d_subkeys, void *d_out, void *stream);
 
+/* ---- 3e. split fan-out: long publishes on a subscriber x segment grid ------------------
+ * Sections 3c and 3d keep a frame on one lane, so a publish takes the time one lane needs for its
+ * blocks whatever the number of subscribers.  Here the lanes are (run, subscriber, segment): a wave
+ * holds 64 subscribers of one run on one segment of the body, so payload, length, flags and block
+ * range are wave-uniform and the plan is one 24-byte record per WAVE -- no descriptor per frame, no
+ * segment record per (frame, segment).  The runs are the cz_fanout_run array of section 3d, unchanged.
+ * Cut points as cz_plan_segments makes them for one seal descriptor of the run's length: a body of
+ * nblk = ceil((len + 33) / 64) blocks stays whole when nblk <= seg_blocks + seg_blocks / 2, and is
+ * ceil(nblk / seg_blocks) segments of seg_blocks blocks otherwise, the last one the remainder.  The
+ * tiles of a split run leave 64-byte Poly1305 partial records in d_work (record part + lane * nseg
+ * for the tile's lane, so a subscriber's nseg records are consecutive), and one join lane per
+ * (split run, subscriber) combines them into the tag at body byte 16.
+ * OUTPUT: for every run, byte for byte what cz_seal_fanout writes for that run alone, ownership
+ * rule of section 3c included; the caller keeps the runs' output ranges disjoint, as in 3d.
+ * A tile's class (CZ_FANOUT_TILE_LINES: a full wave of a 16-byte aligned payload, line-staged
+ * stores; CZ_FANOUT_TILE_DIRECT: partial waves and other payloads, lane-wise) only decides which
+ * launch the wave rides in: a wave re-checks its own run and stores lane-wise when it does not fit
+ * the line emitters, so a table planned for other addresses is slower, never wrong.
+ * A caller may build its own tables: the tiles of one (run, 64 subscribers) cover the body's blocks
+ * [0, nblk) contiguously, one or more blocks each, any lengths, in any order in the table, with
+ * part = the wave's first record + the segment's index and the same nseg in each. */
+typedef struct cz_fanout_tile {
+    uint32_t run;         /* index into the run array */
+    uint32_t first;       /* the wave's lane 0 serves this subscriber of the run (a multiple of 64) */
+    uint32_t first_block; /* first 64-byte box block of the tile */
+    uint32_t nblocks;     /* clipped to the body's block count by the kernel */
+    uint32_t part;        /* lane 0's partial record, 0xffffffff for a body in one tile */
+    uint32_t nseg;        /* segments of the body: lane l writes record part + l * nseg */
+} cz_fanout_tile;          /* 24 bytes */
+typedef struct cz_fanout_join {
+    uint32_t run;   /* index into the run array (a split run) */
+    uint32_t first; /* the wave's lane 0 serves this subscriber of the run (a multiple of 64) */
+    uint32_t part;  /* lane 0's first partial record; lane l combines [part + l * nseg, + nseg) */
+    uint32_t nseg;
+} cz_fanout_join;    /* 16 bytes */
+/* order of the classes in the tile table and in class_count[] */
+#define CZ_FANOUT_TILE_LINES 0
+#define CZ_FANOUT_TILE_DIRECT 1
+/* Host-side planner, no device call; d_in is used as an address only (alignment class).
+ * seg_blocks == 0: the segment length cz_engine_flush_out picks for a batch of the call's total
+ * blocks whose longest body is the longest run's.  Every refusal of cz_plan_fanout applies, checked
+ * before anything is written; more than 2^32 - 1 tiles, join waves or partial records: CZ_EINVAL.
+ * *ntiles = sum over runs of segments x ceil(count / 64), *njoins = sum over split runs of
+ * ceil(count / 64), *npart = sum over split runs of count x segments (d_work must hold 64 bytes
+ * each).  A tile_cap / join_cap below that (or a null table) returns CZ_EINVAL with the three
+ * sizes set and nothing else written, as cz_plan_segments.  class_count[c] = tiles of class c;
+ * inside a class the tiles with the most blocks come first.
+ * Replaces the per-Msg loop of Dist.distribute (zmq/socket/pubsub/Dist.java) -> write(pipe, msg)
+ * -> mechanism.encode, once per message and per pipe. */
+int cz_plan_fanout_split(const cz_fanout_run *h_runs, uint32_t nruns, const void *d_in, uint32_t seg_blocks,
+                         cz_fanout_tile *h_tiles, uint32_t tile_cap, uint32_t *ntiles, uint32_t class_count[2],
+                         cz_fanout_join *h_joins, uint32_t join_cap, uint32_t *njoins, uint32_t *npart);
+/* Dist.distribute (zmq/socket/pubsub/Dist.java) -> write(pipe, msg) -> mechanism.encode, once per
+ * message and per pipe: all of it for R messages, in at most three launches whatever R (tiles of
+ * the line class, lane-wise tiles, join).  d_runs / d_tiles / d_joins: device copies of the run
+ * array and of the planner's tables; class_count as the planner returned it.  Asynchronous on
+ * `stream`; allocates nothing.  nruns == 0 or no tiles: CZ_OK, nothing launched.  Null pointers
+ * (d_joins / d_work only when njoins != 0): CZ_EINVAL, checked before the device is touched.  No
+ * device: CZ_EHIP; there is no CPU fallback. */
+int cz_seal_fanout_split(const cz_fanout_run *d_runs, uint32_t nruns, const cz_fanout_tile *d_tiles,
+                         const uint32_t class_count[2], const cz_fanout_join *d_joins, uint32_t njoins,
+                         const void *d_in, const cz_fanout_sub *d_subs, const void *d_subkeys, void *d_out,
+                         void *d_work, void *stream);
+
 /* Synthetic data: fill d_buf with the counter-based SplitMix64 byte stream (seed). */
 int cz_fill(void *d_buf, uint64_t nbytes, uint64_t seed, void *stream);
 /* Measurement: device-to-device copy of nbytes (a multiple of 16) with 16-byte loads and stores,
@@ -455,8 +519,10 @@ int cz_engine_send(cz_engine *e, int conn, const void *payload, uint32_t len, in
  * An id listed twice gets two frames with consecutive nonces.  flush_out takes a publish's run
  * of at least cz_tune("fanout_min") frames -- or of at least 64 frames with a payload of at most
  * cz_tune("fanout_short") bytes -- out of the segment plan, and seals all such runs of a flush
- * group with one cz_seal_fanout_runs call; the wire bytes are those of the same messages queued
- * with cz_engine_send, whichever way the frames are routed. */
+ * group with one cz_seal_fanout_runs call.  Every other run of at least 64 frames whose payload is
+ * at least cz_tune("fanout_split") bytes leaves the segment plan too, for the group's one
+ * cz_seal_fanout_split call at the flush's own segment length.  The wire bytes are those
+ * of the same messages queued with cz_engine_send, whichever way the frames are routed. */
 int cz_engine_publish(cz_engine *e, const int *conns, uint32_t nconn, const void *payload, uint32_t len,
                       int msg_flags, uint32_t *queued);
 /* seal every queued Msg on the device and V2-frame it into one pinned output in SEND order
@@ -740,7 +806,15 @@ int cz_device_ok(void);
  *              R x N >= 1024 (100 B: 0.0102 against 0.0179 ms for 16 publishes to 1024 subscribers; 256 B:
  *              0.0150 against 0.0198 ms; 1024 B: 0.0395 against 0.0317 ms, so not 1024) and the routed
  *              flush of 256 publishes to 1024 connections is not slower than the segment-plan flush
- *              (100 B: 2.7 against 6.3 ms; 256 B: 3.8 against 5.6 ms); profiles/fanout/fanout_runs.json */
+ *              (100 B: 2.7 against 6.3 ms; 256 B: 3.8 against 5.6 ms); profiles/fanout/fanout_runs.json
+ *   "fanout_split": every other run of at least 64 frames whose payload is at least this many bytes leaves the
+ *              segment plan for the flush group's one cz_seal_fanout_split call (section 3e), cut at the segment
+ *              length the group's segment plan uses, unless fanout_min is 0; 0 = rule off.  Default 4096, the
+ *              smallest measured length from which on the split call is not slower than the segment kernels at
+ *              every R x N >= 1024 (4 KiB: 0.0570 against 0.0612 ms for 16 publishes to 1024 subscribers; 64 KiB:
+ *              0.542 against 0.558 ms; 1 KiB loses one shape, 0.1461 against 0.1460 ms at 2^18 lanes, so not 1024)
+ *              and the routed flush of 256 publishes to 1024 connections is not slower than the segment-plan
+ *              flush (4 KiB: 25.1 against 28.7 ms; 64 KiB: 305 against 307 ms); profiles/fanout/fanout_split.json */
 int cz_tune(const char *key, int value);
 
 #ifdef __cplusplus

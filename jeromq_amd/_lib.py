@@ -102,6 +102,20 @@ assert ctypes.sizeof(cz_fanout_run) == 40 and ctypes.sizeof(cz_fanout_wave) == 8
 CZ_FANOUT_LINES, CZ_FANOUT_REGION, CZ_FANOUT_DIRECT = 0, 1, 2
 
 
+class cz_fanout_tile(ctypes.Structure):
+    _fields_ = [("run", ctypes.c_uint32), ("first", ctypes.c_uint32), ("first_block", ctypes.c_uint32),
+                ("nblocks", ctypes.c_uint32), ("part", ctypes.c_uint32), ("nseg", ctypes.c_uint32)]
+
+
+class cz_fanout_join(ctypes.Structure):
+    _fields_ = [("run", ctypes.c_uint32), ("first", ctypes.c_uint32), ("part", ctypes.c_uint32),
+                ("nseg", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(cz_fanout_tile) == 24 and ctypes.sizeof(cz_fanout_join) == 16
+CZ_FANOUT_TILE_LINES, CZ_FANOUT_TILE_DIRECT = 0, 1
+
+
 class cz_accept_result(ctypes.Structure):
     _fields_ = [("rc", ctypes.c_int32), ("event", ctypes.c_int32), ("slot", ctypes.c_int32),
                 ("reply_len", ctypes.c_uint32)]
@@ -130,6 +144,9 @@ SIGNATURES = {
     "cz_plan_fanout": (_I, [_VP, _U32, _VP, _VP, _VP, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32),
                             ctypes.POINTER(_U32)]),
     "cz_seal_fanout_runs": (_I, [_VP, _U32, _VP, ctypes.POINTER(_U32), _U32, _VP, _VP, _VP, _VP, _VP]),
+    "cz_plan_fanout_split": (_I, [_VP, _U32, _VP, _U32, _VP, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32), _VP,
+                                  _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    "cz_seal_fanout_split": (_I, [_VP, _U32, _VP, ctypes.POINTER(_U32), _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "cz_plan_order": (_I, [_VP, _U32, _VP]),
     "cz_plan_segments": (_I, [_VP, _U32, _I, _U32, _VP, _U32, ctypes.POINTER(_U32), _VP, _U32,
                               ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),

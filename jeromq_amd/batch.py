@@ -122,6 +122,22 @@ def plan_fanout(runs_np, inp, out):
     return FanoutPlan(r, waves[:nw.value], cc, rs.value)
 
 
+def _check_run_bounds(runs_np, inp, out, subs):
+    """Every live run's payload, output range (whole slots where the run owns them) and subscriber
+    records inside their tensors."""
+    live = runs_np[runs_np["count"] > 0]
+    if len(live):
+        ln, cnt = live["len"].astype(np.uint64), live["count"].astype(np.uint64)
+        nsubs = subs.numel() * subs.element_size() // FANOUT_SUB_DTYPE.itemsize
+        st = live["out_stride"]
+        owns = ((st % 128 == 0) & (st < (1 << 25))) | ((st % 16 == 0) & (st <= 256))   # whole slots are written
+        last = np.where(owns, st, ln + np.uint64(33))
+        if (np.any(live["payload_off"] + ln > np.uint64(inp.numel()))
+                or np.any(live["out_off"] + (cnt - np.uint64(1)) * st + last > np.uint64(out.numel()))
+                or np.any(live["first_sub"].astype(np.uint64) + cnt > np.uint64(nsubs))):
+            raise ValueError("run out of bounds")
+
+
 def seal_fanout_runs(plan, inp, subs, subkeys_t, out, stream=None):
     """Grouped PUB fan-out: every run of `plan` (plan_fanout(...).to(device)) sealed in one call of at
     most three launches; run r writes what seal_fanout writes for it alone.  The runs' output ranges
@@ -133,21 +149,85 @@ def seal_fanout_runs(plan, inp, subs, subkeys_t, out, stream=None):
         raise ValueError("subs must be a CUDA (HIP) tensor")
     if plan.nruns and plan.d_runs is None:
         raise ValueError("plan not uploaded: plan.to(device)")
-    live = plan.runs[plan.runs["count"] > 0]
-    if len(live):
-        ln, cnt = live["len"].astype(np.uint64), live["count"].astype(np.uint64)
-        nsubs = subs.numel() * subs.element_size() // FANOUT_SUB_DTYPE.itemsize
-        st = live["out_stride"]
-        owns = ((st % 128 == 0) & (st < (1 << 25))) | ((st % 16 == 0) & (st <= 256))   # whole slots are written
-        last = np.where(owns, st, ln + np.uint64(33))
-        if (np.any(live["payload_off"] + ln > np.uint64(inp.numel()))
-                or np.any(live["out_off"] + (cnt - np.uint64(1)) * st + last > np.uint64(out.numel()))
-                or np.any(live["first_sub"].astype(np.uint64) + cnt > np.uint64(nsubs))):
-            raise ValueError("run out of bounds")
+    _check_run_bounds(plan.runs, inp, out, subs)
     cc = (ctypes.c_uint32 * 3)(*plan.class_count)
     _lib.check(_lib.lib().cz_seal_fanout_runs(_ptr(plan.d_runs), plan.nruns, _ptr(plan.d_waves), cc,
                                               plan.region_stride, _ptr(inp), _ptr(subs), _ptr(subkeys_t), _ptr(out),
                                               _stream(stream)), "cz_seal_fanout_runs")
+
+
+FANOUT_TILE_DTYPE = np.dtype([("run", "<u4"), ("first", "<u4"), ("first_block", "<u4"), ("nblocks", "<u4"),
+                              ("part", "<u4"), ("nseg", "<u4")])
+FANOUT_JOIN_DTYPE = np.dtype([("run", "<u4"), ("first", "<u4"), ("part", "<u4"), ("nseg", "<u4")])
+
+
+class FanoutSplitPlan:
+    """Host plan of a split fan-out (cz_plan_fanout_split): `tiles` (FANOUT_TILE_DTYPE), one per wave of
+    64 subscribers and per segment, sorted by class; `class_count` = tiles of the line / lane-wise class;
+    `joins` (FANOUT_JOIN_DTYPE), one per wave of a split run; `npart` = 64-byte partial records the work
+    buffer must hold.  `to(device)` uploads the three tables.  A caller may replace `tiles`, `joins`,
+    `class_count` and `npart` with tables of its own before `to`."""
+
+    def __init__(self, runs_np, tiles, class_count, joins, npart):
+        self.runs, self.tiles, self.joins = runs_np, tiles, joins
+        self.class_count, self.npart = list(class_count), npart
+        self.nruns = len(runs_np)
+        self.d_runs = self.d_tiles = self.d_joins = None
+
+    def to(self, device):
+        import torch
+
+        def up(a, dt):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=dt).view(np.uint8).copy()).to(device)
+        self.d_runs = up(self.runs, FANOUT_RUN_DTYPE)
+        self.d_tiles = up(self.tiles, FANOUT_TILE_DTYPE)
+        self.d_joins = up(self.joins, FANOUT_JOIN_DTYPE)
+        return self
+
+
+def plan_fanout_split(runs_np, inp, out, seg_blocks=0):
+    """Plan the split fan-out of `runs_np` (FANOUT_RUN_DTYPE) reading `inp` (a device tensor or a plain
+    address, used for its 16-byte alignment only) and writing `out` (not looked at: the kernel picks the
+    emitter from the output's alignment itself).  seg_blocks 0: the engine's choice for a batch of this
+    size.  Returns a FanoutSplitPlan."""
+    r = np.ascontiguousarray(runs_np, dtype=FANOUT_RUN_DTYPE)
+    a_in = inp if isinstance(inp, int) else inp.data_ptr()
+    nt, nj, npart, cc = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32(), (ctypes.c_uint32 * 2)()
+    L = _lib.lib()
+    L.cz_plan_fanout_split(r.ctypes.data, len(r), a_in, seg_blocks, None, 0, ctypes.byref(nt), cc, None, 0,
+                           ctypes.byref(nj), ctypes.byref(npart))
+    tiles = np.zeros(max(nt.value, 1), dtype=FANOUT_TILE_DTYPE)
+    joins = np.zeros(max(nj.value, 1), dtype=FANOUT_JOIN_DTYPE)
+    _lib.check(L.cz_plan_fanout_split(r.ctypes.data, len(r), a_in, seg_blocks, tiles.ctypes.data, len(tiles),
+                                      ctypes.byref(nt), cc, joins.ctypes.data, len(joins), ctypes.byref(nj),
+                                      ctypes.byref(npart)), "cz_plan_fanout_split")
+    return FanoutSplitPlan(r, tiles[:nt.value], cc, joins[:nj.value], npart.value)
+
+
+def seal_fanout_split(plan, inp, subs, subkeys_t, out, work=None, stream=None):
+    """Split PUB fan-out: every run of `plan` (plan_fanout_split(...).to(device)) sealed on a subscriber x
+    segment grid in at most three launches; run r writes what seal_fanout writes for it alone.  The runs'
+    output ranges must not overlap.  `work`: 64 * plan.npart bytes of device scratch, allocated when not
+    given.  Bounds are checked against the plan's host copy of the runs."""
+    import torch
+    _need_cuda_u8(inp, "in")
+    _need_cuda_u8(out, "out")
+    _need_cuda_u8(subkeys_t, "subkeys")
+    if subs is None or not subs.is_cuda:
+        raise ValueError("subs must be a CUDA (HIP) tensor")
+    if plan.nruns and plan.d_runs is None:
+        raise ValueError("plan not uploaded: plan.to(device)")
+    _check_run_bounds(plan.runs, inp, out, subs)
+    if work is None:
+        work = torch.empty(max(plan.npart, 1) * 64, dtype=torch.uint8, device=out.device)
+    elif work.numel() * work.element_size() < 64 * plan.npart:
+        raise ValueError("work smaller than 64 * plan.npart bytes")
+    cc = (ctypes.c_uint32 * 2)(*plan.class_count)
+    _lib.check(_lib.lib().cz_seal_fanout_split(_ptr(plan.d_runs), plan.nruns, _ptr(plan.d_tiles), cc,
+                                               _ptr(plan.d_joins), len(plan.joins), _ptr(inp), _ptr(subs),
+                                               _ptr(subkeys_t), _ptr(out), _ptr(work), _stream(stream)),
+               "cz_seal_fanout_split")
+    return work
 
 
 def seal_uniform_box(box, box_stride, out, out_stride, count, length, subkey, counter0, stream=None):

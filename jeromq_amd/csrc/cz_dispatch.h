@@ -82,7 +82,7 @@ struct Knobs {
 };
 
 // ---- what a launcher launches -----------------------------------------------
-enum Family { K_SEAL_UNIFORM, K_SEAL_UNIFORM_INA, K_SEAL_FANOUT, K_OPEN_UNIFORM, K_OPEN_UNIFORM_CARRY };
+enum Family { K_SEAL_UNIFORM, K_SEAL_UNIFORM_INA, K_SEAL_FANOUT, K_OPEN_UNIFORM, K_OPEN_UNIFORM_CARRY, K_SEAL_FANOUT_TILES };
 constexpr int64_t PAD_NONE = -1;
 
 struct Launch {
@@ -230,6 +230,15 @@ inline Launch plan_fanout_runs(int cls, uint32_t nwaves, uint32_t part16)
     const int st = cls == CZ_FANOUT_LINES ? ST_LINES : (cls == CZ_FANOUT_REGION ? ST_REGION : ST_DIRECT);
     return Launch{K_SEAL_FANOUT, st, st != ST_REGION, 16, MODE_ZMQ, (nwaves + WAVES - 1) / WAVES,
                   st == ST_REGION ? (uint32_t)(WAVES * 16u * part16) : staging_lds(st, 0, true), PAD_NONE};
+}
+
+// czk_seal_fanout_split: one class's slice of the tile table, one wave per tile; the line class stages
+// through the segment emitters' rows (EmitSegLines / EmitShiftLines), the lane-wise class needs no LDS
+inline Launch plan_fanout_tiles(int cls, uint32_t ntiles)
+{
+    const int st = cls == CZ_FANOUT_TILE_LINES ? ST_LINES : ST_DIRECT;
+    return Launch{K_SEAL_FANOUT_TILES, st, true, 16, MODE_ZMQ, (ntiles + WAVES - 1) / WAVES,
+                  st == ST_LINES ? WAVES * SHIFT_LDS_BYTES : 0u, PAD_NONE};
 }
 
 // czk_open_uniform: `count` MESSAGE bodies of `size` bytes at in + i * in_stride to plaintext at out + i * out_stride

@@ -189,13 +189,15 @@ struct OutMsg {
 // flags, and their body slots are contiguous at one stride.
 struct FanRun {
     uint32_t first, count;
+    bool split;  // the group's cz_seal_fanout_split call (subscriber x segment grid) instead
 };
 
 // The fan-out runs of pend[fa, fb): maximal runs of consecutive frames of one publish with at
 // least `min_run` frames, or with at least one full wave of frames and a payload of at most
-// `short_len` bytes (0: that rule off).  min_run 0: none.
+// `short_len` bytes (0: that rule off).  Of the other runs, those with at least one full wave of
+// frames and a payload of at least `split_len` bytes (0: off) are split runs.  min_run 0: none.
 void fanout_runs(const std::vector<OutMsg> &pend, uint32_t fa, uint32_t fb, uint32_t min_run, uint32_t short_len,
-                 std::vector<FanRun> &runs)
+                 uint32_t split_len, std::vector<FanRun> &runs)
 {
     runs.clear();
     if (min_run == 0)
@@ -206,7 +208,9 @@ void fanout_runs(const std::vector<OutMsg> &pend, uint32_t fa, uint32_t fb, uint
             while (j < fb && pend[j].pub == pend[i].pub)
                 j++;
         if (pend[i].pub && (j - i >= min_run || (short_len && j - i >= 64u && pend[i].len <= short_len)))
-            runs.push_back({i, j - i});
+            runs.push_back({i, j - i, false});
+        else if (pend[i].pub && split_len && j - i >= 64u && pend[i].len >= split_len)
+            runs.push_back({i, j - i, true});
         i = j;
     }
 }
@@ -259,7 +263,8 @@ struct cz_engine {
     std::vector<InMsg> in_msgs;
     // device staging (grows, never shrinks)
     DevBuf d_in, d_body, d_wire, d_desc, d_seg, d_comb, d_work, d_items, d_status, d_nonces, d_plain, d_subs,
-        d_fruns, d_fwaves;  // grouped fan-out: run and wave tables
+        d_fruns, d_fwaves,  // grouped fan-out: run and wave tables
+        d_ftiles, d_fjoins, d_fwork;  // split fan-out: tile and join tables, partial records
     uint32_t pub_seq = 0;  // id of the last cz_engine_publish call (OutMsg::pub)
     HostBuf h_status, h_nonces;
     HostBuf h_meta;  // pinned staging of descriptors / items / segment lists (async H2D)
@@ -293,7 +298,8 @@ struct cz_engine {
                 (void)hipStreamDestroy(q);
             }
         for (DevBuf *b : {&subkeys, &d_in, &d_body, &d_wire, &d_desc, &d_seg, &d_comb, &d_work, &d_items, &d_status,
-                          &d_nonces, &d_plain, &d_subs, &d_fruns, &d_fwaves, &d_stage})
+                          &d_nonces, &d_plain, &d_subs, &d_fruns, &d_fwaves, &d_ftiles, &d_fjoins,
+                          &d_fwork, &d_stage})
             b->release();
         for (HostBuf *b : {&arena, &h_wire, &h_plain, &h_status, &h_nonces, &h_meta, &h_stage})
             b->release();
@@ -389,21 +395,35 @@ struct cz_engine {
         // publishes: inside a group, a run of one publish's frames has contiguous body slots of
         // one stride (slots follow send order) and leaves the segment plan for the group's one
         // cz_seal_fanout_runs call; a publish split by a group edge is two runs.  fan[i]: frame i
-        // is in such a run.  roff / fwoff: the groups' ranges in the run and wave tables.
+        // is in such a run.  roff / fwoff: the groups' ranges in the run and wave tables.  The split
+        // runs of a group (cz_tune "fanout_split") are its one cz_seal_fanout_split call at the
+        // flush's segment length: toff / joff / pwoff, its ranges of tiles, joins and partial records.
         std::vector<std::vector<FanRun>> fruns(groups.size());
         std::vector<uint8_t> fan(n, 0);
-        std::vector<uint64_t> roff(groups.size() + 1, 0), fwoff(groups.size() + 1, 0);
-        const uint32_t fan_min = fanout_min(), fan_short = fanout_short();
+        std::vector<uint64_t> roff(groups.size() + 1, 0), fwoff(groups.size() + 1, 0), toff(groups.size() + 1, 0),
+            joff(groups.size() + 1, 0), pwoff(groups.size() + 1, 0);
+        const uint32_t fan_min = fanout_min(), fan_short = fanout_short(), fan_split = fanout_split();
         for (size_t gi = 0; gi < groups.size(); gi++) {
-            fanout_runs(pend, groups[gi].fa, groups[gi].fb, fan_min, fan_short, fruns[gi]);
+            fanout_runs(pend, groups[gi].fa, groups[gi].fb, fan_min, fan_short, fan_split, fruns[gi]);
             roff[gi + 1] = roff[gi] + fruns[gi].size();
             fwoff[gi + 1] = fwoff[gi];
+            std::vector<cz_fanout_run> split;  // (length and count are all the counts need)
             for (const FanRun &r : fruns[gi]) {
                 std::fill(fan.begin() + r.first, fan.begin() + r.first + r.count, (uint8_t)1);
-                fwoff[gi + 1] += ((uint64_t)r.count + 63) / 64;
+                if (r.split)
+                    split.push_back({0, 0, 0, pend[r.first].len, 0, 0, r.count});
+                else
+                    fwoff[gi + 1] += ((uint64_t)r.count + 63) / 64;
             }
+            const FanoutSplitCounts sc = fanout_split_counts(split.data(), (uint32_t)split.size(), seg);
+            if (sc.ntiles > 0xffffffffull || sc.npart > 0xffffffffull)
+                return fail(CZ_EINVAL, "cz_engine: more than 2^32 - 1 fan-out tiles in a flush group");
+            toff[gi + 1] = toff[gi] + sc.ntiles;
+            joff[gi + 1] = joff[gi] + sc.njoins;
+            pwoff[gi + 1] = pwoff[gi] + sc.npart;
         }
-        const uint64_t nfrun = roff[groups.size()], nfwave = fwoff[groups.size()];
+        const uint64_t nfrun = roff[groups.size()], nfwave = fwoff[groups.size()], nftile = toff[groups.size()],
+                       nfjoin = joff[groups.size()], nfpart = pwoff[groups.size()];
         const bool any_fan = nfrun != 0;
         std::vector<uint64_t> soff(groups.size() + 1, 0), coff(groups.size() + 1, 0), woff(groups.size() + 1, 0);
         uint64_t slot = 0, hi = 0;
@@ -429,7 +449,9 @@ struct cz_engine {
                        m_subs = m_comb + ncomb * sizeof(cz_combine),
                        m_fruns = m_subs + (any_fan ? (uint64_t)n * sizeof(cz_fanout_sub) : 0),
                        m_fwaves = m_fruns + nfrun * sizeof(cz_fanout_run),
-                       m_end = m_fwaves + nfwave * sizeof(cz_fanout_wave);
+                       m_ftiles = m_fwaves + nfwave * sizeof(cz_fanout_wave),
+                       m_fjoins = m_ftiles + nftile * sizeof(cz_fanout_tile),
+                       m_end = m_fjoins + nfjoin * sizeof(cz_fanout_join);
         hipError_t e;
         if ((e = d_in.reserve(std::max<uint64_t>(arena_used, 16))) != hipSuccess ||
             (e = d_body.reserve(slot)) != hipSuccess || (e = d_wire.reserve(wire_total)) != hipSuccess ||
@@ -440,7 +462,10 @@ struct cz_engine {
             (e = d_work.reserve(std::max<uint64_t>(npart, 1) * 64)) != hipSuccess ||
             (any_fan && ((e = d_subs.reserve((uint64_t)n * sizeof(cz_fanout_sub))) != hipSuccess ||
                          (e = d_fruns.reserve(nfrun * sizeof(cz_fanout_run))) != hipSuccess ||
-                         (e = d_fwaves.reserve(nfwave * sizeof(cz_fanout_wave))) != hipSuccess)) ||
+                         (e = d_fwaves.reserve(nfwave * sizeof(cz_fanout_wave))) != hipSuccess ||
+                         (e = d_ftiles.reserve(nftile * sizeof(cz_fanout_tile))) != hipSuccess ||
+                         (e = d_fjoins.reserve(nfjoin * sizeof(cz_fanout_join))) != hipSuccess ||
+                         (e = d_fwork.reserve(nfpart * 64)) != hipSuccess)) ||
             (e = h_wire.reserve(wire_total)) != hipSuccess || (e = h_meta.reserve(m_end)) != hipSuccess)
             return hip_fail(e, "cz_engine: alloc");
         // descriptors and items are built straight into pinned staging (pageable sources would
@@ -451,6 +476,8 @@ struct cz_engine {
         cz_fanout_sub *h_subs = (cz_fanout_sub *)(hm + m_subs);  // by send index, fan-out frames only
         cz_fanout_run *h_fruns = (cz_fanout_run *)(hm + m_fruns);
         cz_fanout_wave *h_fwaves = (cz_fanout_wave *)(hm + m_fwaves);
+        cz_fanout_tile *h_ftiles = (cz_fanout_tile *)(hm + m_ftiles);
+        cz_fanout_join *h_fjoins = (cz_fanout_join *)(hm + m_fjoins);
         pt.mark("plan");
         std::vector<hipEvent_t> ev(groups.size(), nullptr), evk(groups.size(), nullptr);
         EvGuard evguard{ev}, evkguard{evk};
@@ -498,20 +525,30 @@ struct cz_engine {
             // one copy for the group's subscriber records: first run's start to last run's end
             const uint32_t sub_a = fr.empty() ? 0u : fr.front().first,
                            sub_b = fr.empty() ? 0u : fr.back().first + fr.back().count;
-            // the group's run table (a run's first_sub is its send index) and wave table
-            const uint32_t gfr = (uint32_t)fr.size(), gfw = (uint32_t)(fwoff[gi + 1] - fwoff[gi]);
+            // the group's run table (a run's first_sub is its send index): the gfr grouped runs and
+            // their wave table, then the gsr split runs with their tile and join tables
+            const uint32_t gsr = (uint32_t)std::count_if(fr.begin(), fr.end(), [](const FanRun &r) { return r.split; });
+            const uint32_t gfr = (uint32_t)fr.size() - gsr, gfw = (uint32_t)(fwoff[gi + 1] - fwoff[gi]);
+            const uint32_t gst = (uint32_t)(toff[gi + 1] - toff[gi]), gsj = (uint32_t)(joff[gi + 1] - joff[gi]);
             cz_fanout_run *hr = h_fruns + roff[gi];
-            uint32_t fclass[3] = {0, 0, 0}, fregion = 0;
-            for (uint32_t k = 0; k < gfr; k++) {
-                const OutMsg &m = pend[fr[k].first];
-                hr[k] = {m.arena_off, h_items[fr[k].first].src_off,
-                         round_up((uint64_t)m.len + CZ_MESSAGE_OVERHEAD, SLOT_ALIGN), m.len, m.flags & 0xffu,
-                         fr[k].first, fr[k].count};
+            uint32_t fclass[3] = {0, 0, 0}, fregion = 0, sclass[2] = {0, 0};
+            uint32_t kf = 0, ks = gfr;
+            for (const FanRun &r : fr) {
+                const OutMsg &m = pend[r.first];
+                hr[r.split ? ks++ : kf++] = {m.arena_off, h_items[r.first].src_off,
+                                             round_up((uint64_t)m.len + CZ_MESSAGE_OVERHEAD, SLOT_ALIGN), m.len,
+                                             m.flags & 0xffu, r.first, r.count};
             }
             if (gfr)
                 fregion = plan_fanout(hr, gfr, d_in.ptr, d_body.ptr, h_fwaves + fwoff[gi], fclass);
+            if (gsr)
+                plan_fanout_split(hr + gfr, gsr, d_in.ptr, seg, h_ftiles + toff[gi], sclass, h_fjoins + joff[gi]);
+            if (sclass[0] + sclass[1] != gst)
+                return fail(CZ_EINVAL, "cz_engine: fan-out tile plan disagrees with its count");
             const cz_fanout_run *dfr = (const cz_fanout_run *)d_fruns.ptr + roff[gi];
             const cz_fanout_wave *dfw = (const cz_fanout_wave *)d_fwaves.ptr + fwoff[gi];
+            const cz_fanout_tile *dft = (const cz_fanout_tile *)d_ftiles.ptr + toff[gi];
+            const cz_fanout_join *dfj = (const cz_fanout_join *)d_fjoins.ptr + joff[gi];
             plan_segments(h_desc + g.fa, gd, 0, seg, sg.seg, sg.comb, sg.npart);
             const uint32_t gseg = (uint32_t)sg.seg.size(), gcomb = (uint32_t)sg.comb.size();
             if (gseg != soff[gi + 1] - soff[gi] || gcomb != coff[gi + 1] - coff[gi] || sg.npart != woff[gi + 1] - woff[gi])
@@ -530,10 +567,14 @@ struct cz_engine {
                 (sub_b > sub_a && (e = hipMemcpyAsync((cz_fanout_sub *)d_subs.ptr + sub_a, h_subs + sub_a,
                                                       (uint64_t)(sub_b - sub_a) * sizeof(cz_fanout_sub),
                                                       hipMemcpyHostToDevice, qh)) != hipSuccess) ||
-                (gfr && ((e = hipMemcpyAsync((void *)dfr, hr, (uint64_t)gfr * sizeof(cz_fanout_run), hipMemcpyHostToDevice,
-                                             qh)) != hipSuccess ||
-                         (e = hipMemcpyAsync((void *)dfw, h_fwaves + fwoff[gi], (uint64_t)gfw * sizeof(cz_fanout_wave),
-                                             hipMemcpyHostToDevice, qh)) != hipSuccess)) ||
+                (gfr + gsr && (e = hipMemcpyAsync((void *)dfr, hr, (uint64_t)(gfr + gsr) * sizeof(cz_fanout_run),
+                                                  hipMemcpyHostToDevice, qh)) != hipSuccess) ||
+                (gfr && (e = hipMemcpyAsync((void *)dfw, h_fwaves + fwoff[gi], (uint64_t)gfw * sizeof(cz_fanout_wave),
+                                            hipMemcpyHostToDevice, qh)) != hipSuccess) ||
+                (gst && (e = hipMemcpyAsync((void *)dft, h_ftiles + toff[gi], (uint64_t)gst * sizeof(cz_fanout_tile),
+                                            hipMemcpyHostToDevice, qh)) != hipSuccess) ||
+                (gsj && (e = hipMemcpyAsync((void *)dfj, h_fjoins + joff[gi], (uint64_t)gsj * sizeof(cz_fanout_join),
+                                            hipMemcpyHostToDevice, qh)) != hipSuccess) ||
                 (gseg &&(e = hipMemcpyAsync(dsg, (const cz_segment *)(hm + m_seg) + soff[gi],
                                              (uint64_t)gseg * sizeof(cz_segment), hipMemcpyHostToDevice, qh)) !=
                              hipSuccess) ||
@@ -550,6 +591,10 @@ struct cz_engine {
             if (gfr && (e = czk_seal_fanout_runs(dfr, dfw, fclass, fregion, d_in.ptr, (const cz_fanout_sub *)d_subs.ptr,
                                                  subkeys.ptr, d_body.ptr, qk)) != hipSuccess)
                 return hip_fail(e, "cz_engine: flush_out fan-out");
+            if (gsr && (e = czk_seal_fanout_split(dfr + gfr, dft, sclass, dfj, gsj, d_in.ptr, (const cz_fanout_sub *)d_subs.ptr,
+                                                  subkeys.ptr, d_body.ptr, (uint8_t *)d_fwork.ptr + 64 * pwoff[gi],
+                                                  qk)) != hipSuccess)
+                return hip_fail(e, "cz_engine: flush_out split fan-out");
             if ((gseg &&(e = czk_seal_segments(dd, dsg, gseg, dcb, gcomb, d_in.ptr, d_body.ptr, subkeys.ptr,
                                                 (uint8_t *)d_work.ptr + 64 * woff[gi], qk)) != hipSuccess) ||
                 (e = czk_v2_copy((const cz_v2_item *)d_items.ptr + g.fa, gn, d_body.ptr, d_wire.ptr, qk)) !=

@@ -264,6 +264,25 @@ static std::atomic<uint64_t> g_fanout_short{256};
 
 uint32_t fanout_short() { return (uint32_t)g_fanout_short.load(std::memory_order_relaxed); }
 
+// cz_engine_flush_out: a publish's run of at least 64 frames (one full wave) whose payload is at least
+// this many bytes leaves the segment plan for the group's one cz_seal_fanout_split call, cut at the
+// group's own segment length, unless fanout_min is 0; 0 = rule off (cz_tune "fanout_split").  Runs that
+// fanout_min or fanout_short route keep going to cz_seal_fanout_runs.
+// Default 4096, by the rule set before the run: the smallest measured length L (of 1024, 4096, 16 384,
+// 65 536) such that at every measured length >= L the split call (e) is not slower than the segment
+// kernels at the flush's own segment length (b') in the median at every measured R x N >= 1024, and the
+// flush routed by it is not slower than the segment-plan flush (tools/fanout_bench.py --split,
+// profiles/fanout/fanout_split.json, medians of 7, legs interleaved):
+//   len     (e) / (b') ms at R x N = 1024, 16 384, 262 144             256 x publish to 1024, flush ms
+//   1024    0.0185 / 0.0208   0.0273 / 0.0311   0.1461 / 0.1460        9.28 routed, 11.03 segment plan
+//   4096    0.0321 / 0.0361   0.0570 / 0.0612   0.4845 / 0.4950        25.1 routed, 28.7 segment plan
+//   16384   0.0517 / 0.0571   0.1750 / 0.1832   1.8489 / 1.8824        78.7 routed, 79.8 segment plan
+//   65536   0.0901 / 0.0964   0.5424 / 0.5579   7.2325 / 7.3673        305.3 routed, 307.4 segment plan
+// 1024 B loses one shape by 0.1% (2^18 lanes, where its 17-block bodies stay whole in both paths), so not 1024.
+static std::atomic<uint64_t> g_fanout_split{4096};
+
+uint32_t fanout_split() { return (uint32_t)g_fanout_split.load(std::memory_order_relaxed); }
+
 // NaCl box/open of one message on the device.  A MESSAGE is the NaCl box of
 // 0^32 || flags || payload, so m[32] rides as the flags byte and m[33:] as the payload; for open
 // the 16 bytes ahead of the tag are rebuilt as "\x07MESSAGE" || n[16:24] and the nonce check is off.
@@ -503,6 +522,81 @@ uint32_t plan_fanout(const cz_fanout_run *runs, uint32_t nruns, const void *d_in
     return region_stride;
 }
 
+// Split fan-out (cz_plan_fanout_split).  A run's cut points are plan_segments' for one seal descriptor
+// of its length: whole up to 1.5 x seg_blocks blocks, else ceil(nblk / seg_blocks) segments.
+static uint32_t run_blocks(const cz_fanout_run &f) { return (uint32_t)(((uint64_t)f.len + CZ_MESSAGE_OVERHEAD + 63) / 64); }
+static uint32_t run_segments(const cz_fanout_run &f, uint32_t seg_blocks)
+{
+    const uint32_t nblk = run_blocks(f);
+    return nblk <= seg_blocks + seg_blocks / 2 ? 1u : (nblk + seg_blocks - 1) / seg_blocks;
+}
+
+uint32_t fanout_split_seg_blocks(const cz_fanout_run *runs, uint32_t nruns)
+{
+    uint64_t total = 0, longest = 1;
+    for (uint32_t r = 0; r < nruns; r++) {
+        if (runs[r].count == 0)
+            continue;
+        total += (uint64_t)runs[r].count * run_blocks(runs[r]);
+        longest = std::max<uint64_t>(longest, run_blocks(runs[r]));
+    }
+    return batch_seg_blocks(total, longest);
+}
+
+FanoutSplitCounts fanout_split_counts(const cz_fanout_run *runs, uint32_t nruns, uint32_t seg_blocks)
+{
+    FanoutSplitCounts c{0, 0, 0};
+    for (uint32_t r = 0; r < nruns; r++) {
+        const uint64_t waves = ((uint64_t)runs[r].count + 63) / 64, ns = run_segments(runs[r], seg_blocks);
+        c.ntiles += waves * ns;
+        if (ns > 1) {
+            c.njoins += waves;
+            c.npart += (uint64_t)runs[r].count * ns;
+        }
+    }
+    return c;
+}
+
+// Tiles in run, segment, wave order, then a stable sort by class and block count (most blocks first),
+// so the waves of one (run, segment) -- the same payload lines -- stay neighbours and a long tile
+// does not start last.  A full wave of a 16-byte aligned payload is of the line class.
+void plan_fanout_split(const cz_fanout_run *runs, uint32_t nruns, const void *d_in, uint32_t seg_blocks,
+                       cz_fanout_tile *tiles, uint32_t class_count[2], cz_fanout_join *joins)
+{
+    std::vector<cz_fanout_tile> all;
+    std::vector<uint8_t> cls;
+    uint64_t part = 0;
+    uint32_t nj = 0;
+    for (uint32_t r = 0; r < nruns; r++) {
+        const cz_fanout_run &f = runs[r];
+        const uint32_t nblk = run_blocks(f), ns = run_segments(f, seg_blocks);
+        const bool in_al = (((uintptr_t)d_in + f.payload_off) & 15u) == 0;
+        for (uint32_t s = 0; s < ns; s++) {
+            const uint32_t b0 = ns > 1 ? s * seg_blocks : 0u, b1 = s + 1 < ns ? (s + 1) * seg_blocks : nblk;
+            for (uint64_t first = 0; first < f.count; first += 64) {
+                const uint32_t p = ns > 1 ? (uint32_t)(part + first * ns + s) : 0xffffffffu;
+                all.push_back({r, (uint32_t)first, b0, b1 - b0, p, ns});
+                cls.push_back(in_al && first + 64 <= f.count ? CZ_FANOUT_TILE_LINES : CZ_FANOUT_TILE_DIRECT);
+            }
+        }
+        if (ns > 1) {
+            for (uint64_t first = 0; first < f.count; first += 64)
+                joins[nj++] = {r, (uint32_t)first, (uint32_t)(part + first * ns), ns};
+            part += (uint64_t)f.count * ns;
+        }
+    }
+    std::vector<uint32_t> order(all.size());
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        return cls[a] != cls[b] ? cls[a] < cls[b] : all[a].nblocks > all[b].nblocks;
+    });
+    class_count[0] = class_count[1] = 0;
+    for (size_t k = 0; k < order.size(); k++) {
+        tiles[k] = all[order[k]];
+        class_count[cls[order[k]]]++;
+    }
+}
+
 }  // namespace czi
 
 using namespace czi;
@@ -538,7 +632,8 @@ int cz_tune(const char *key, int value)
     // the host's own knobs (relaxed atomics: IO threads read them), then the kernels' (czk_tune)
     const struct { const char *name; std::atomic<uint64_t> *knob; uint64_t max; } host_knobs[] = {
         {"nacl_one_max", &g_nacl_one_bytes, czk_nacl_one_limit()},  // bytes; at least one pass of k_nacl_one
-        {"fanout_min", &g_fanout_min, INT32_MAX}, {"fanout_short", &g_fanout_short, INT32_MAX}};
+        {"fanout_min", &g_fanout_min, INT32_MAX}, {"fanout_short", &g_fanout_short, INT32_MAX},
+        {"fanout_split", &g_fanout_split, INT32_MAX}};
     for (const auto &h : host_knobs)
         if (key && strcmp(key, h.name) == 0) {
             const int old = (int)h.knob->load(std::memory_order_relaxed);
@@ -684,26 +779,34 @@ int cz_seal_fanout(uint32_t count, uint32_t len, const void *d_payload, uint32_t
     return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_seal_fanout");
 }
 
+// what cz_plan_fanout and cz_plan_fanout_split refuse in a run array, before anything is written
+static int check_fanout_runs(const char *who, const cz_fanout_run *h_runs, uint32_t nruns)
+{
+    for (uint32_t r = 0; r < nruns; r++) {
+        const cz_fanout_run &f = h_runs[r];
+        uint64_t span = 0;
+        if (f.len > (uint32_t)CZ_MESSAGE_MAX)
+            return fail(CZ_EMSGSIZE, "%s: run %u: %u-byte payload exceeds CZ_MESSAGE_MAX", who, r, f.len);
+        if (f.out_stride < (uint64_t)f.len + CZ_MESSAGE_OVERHEAD)
+            return fail(CZ_EINVAL, "%s: run %u: out_stride smaller than the body", who, r);
+        if ((uint64_t)f.first_sub + f.count > 0xffffffffull)
+            return fail(CZ_EINVAL, "%s: run %u: first_sub + count overflows", who, r);
+        // (the whole slots of an owning run, as uniform_span: within a 2^47-byte address range)
+        if (__builtin_mul_overflow((uint64_t)f.count, f.out_stride, &span) ||
+            __builtin_add_overflow(span, f.out_off, &span) || span > (1ull << 47))
+            return fail(CZ_EINVAL, "%s: run %u: out_off + count x out_stride overflows the address space", who, r);
+    }
+    return CZ_OK;
+}
+
 int cz_plan_fanout(const cz_fanout_run *h_runs, uint32_t nruns, const void *d_in, const void *d_out,
                    cz_fanout_wave *h_waves, uint32_t wave_cap, uint32_t *nwaves, uint32_t class_count[3],
                    uint32_t *region_stride)
 {
     if ((nruns && (!h_runs || !d_in || !d_out)) || !nwaves || !class_count || !region_stride)
         return fail(CZ_EINVAL, "cz_plan_fanout: null pointer");
-    for (uint32_t r = 0; r < nruns; r++) {
-        const cz_fanout_run &f = h_runs[r];
-        uint64_t span = 0;
-        if (f.len > (uint32_t)CZ_MESSAGE_MAX)
-            return fail(CZ_EMSGSIZE, "cz_plan_fanout: run %u: %u-byte payload exceeds CZ_MESSAGE_MAX", r, f.len);
-        if (f.out_stride < (uint64_t)f.len + CZ_MESSAGE_OVERHEAD)
-            return fail(CZ_EINVAL, "cz_plan_fanout: run %u: out_stride smaller than the body", r);
-        if ((uint64_t)f.first_sub + f.count > 0xffffffffull)
-            return fail(CZ_EINVAL, "cz_plan_fanout: run %u: first_sub + count overflows", r);
-        // (the whole slots of an owning run, as uniform_span: within a 2^47-byte address range)
-        if (__builtin_mul_overflow((uint64_t)f.count, f.out_stride, &span) ||
-            __builtin_add_overflow(span, f.out_off, &span) || span > (1ull << 47))
-            return fail(CZ_EINVAL, "cz_plan_fanout: run %u: out_off + count x out_stride overflows the address space", r);
-    }
+    if (int rc = check_fanout_runs("cz_plan_fanout", h_runs, nruns))
+        return rc;
     const uint64_t need = fanout_waves(h_runs, nruns);
     if (need > 0xffffffffull)
         return fail(CZ_EINVAL, "cz_plan_fanout: more than 2^32 waves");
@@ -730,6 +833,50 @@ int cz_seal_fanout_runs(const cz_fanout_run *d_runs, uint32_t nruns, const cz_fa
     hipError_t e = czk_seal_fanout_runs(d_runs, d_waves, class_count, region_stride, d_in, d_subs, d_subkeys, d_out,
                                         (hipStream_t)stream);
     return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_seal_fanout_runs");
+}
+
+int cz_plan_fanout_split(const cz_fanout_run *h_runs, uint32_t nruns, const void *d_in, uint32_t seg_blocks,
+                         cz_fanout_tile *h_tiles, uint32_t tile_cap, uint32_t *ntiles, uint32_t class_count[2],
+                         cz_fanout_join *h_joins, uint32_t join_cap, uint32_t *njoins, uint32_t *npart)
+{
+    if ((nruns && (!h_runs || !d_in)) || !ntiles || !class_count || !njoins || !npart)
+        return fail(CZ_EINVAL, "cz_plan_fanout_split: null pointer");
+    if (int rc = check_fanout_runs("cz_plan_fanout_split", h_runs, nruns))
+        return rc;
+    if (seg_blocks == 0)
+        seg_blocks = fanout_split_seg_blocks(h_runs, nruns);
+    const FanoutSplitCounts c = fanout_split_counts(h_runs, nruns, seg_blocks);
+    // (tile and join indices are 32-bit; 0xffffffff in a tile's `part` means a body in one tile)
+    if (c.ntiles > 0xffffffffull || c.npart > 0xffffffffull)
+        return fail(CZ_EINVAL, "cz_plan_fanout_split: more than 2^32 - 1 tiles or partial records");
+    *ntiles = (uint32_t)c.ntiles;
+    *njoins = (uint32_t)c.njoins;
+    *npart = (uint32_t)c.npart;
+    if (c.ntiles > tile_cap || c.njoins > join_cap || (c.ntiles && !h_tiles) || (c.njoins && !h_joins))
+        return fail(CZ_EINVAL, "cz_plan_fanout_split: capacity too small (need %u tiles, %u joins)", *ntiles, *njoins);
+    plan_fanout_split(h_runs, nruns, d_in, seg_blocks, h_tiles, class_count, h_joins);
+    return CZ_OK;
+}
+
+int cz_seal_fanout_split(const cz_fanout_run *d_runs, uint32_t nruns, const cz_fanout_tile *d_tiles,
+                         const uint32_t class_count[2], const cz_fanout_join *d_joins, uint32_t njoins,
+                         const void *d_in, const cz_fanout_sub *d_subs, const void *d_subkeys, void *d_out,
+                         void *d_work, void *stream)
+{
+    if (!class_count)
+        return fail(CZ_EINVAL, "cz_seal_fanout_split: null pointer");
+    const uint64_t ntiles = (uint64_t)class_count[0] + class_count[1];
+    if (nruns == 0 || ntiles == 0)
+        return CZ_OK;
+    if (!d_runs || !d_tiles || !d_in || !d_subs || !d_subkeys || !d_out)
+        return fail(CZ_EINVAL, "cz_seal_fanout_split: null pointer");
+    if (njoins && (!d_joins || !d_work))
+        return fail(CZ_EINVAL, "cz_seal_fanout_split: null join table / workspace");
+    if (ntiles > 0xffffffffull)
+        return fail(CZ_EINVAL, "cz_seal_fanout_split: more than 2^32 - 1 tiles");
+    hipError_t e = czk_seal_fanout_split(d_runs, d_tiles, class_count, d_joins, njoins, d_in, d_subs, d_subkeys, d_out,
+                                         d_work, (hipStream_t)stream);
+    return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_seal_fanout_split");
 }
 
 int cz_seal_uniform_box(uint32_t count, uint32_t len, const void *d_box, uint64_t box_stride, void *d_out,

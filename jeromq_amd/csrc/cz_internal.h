@@ -32,6 +32,17 @@ uint64_t fanout_waves(const cz_fanout_run *runs, uint32_t nruns);
 uint32_t plan_fanout(const cz_fanout_run *runs, uint32_t nruns, const void *d_in, const void *d_out, cz_fanout_wave *waves,
                      uint32_t class_count[3]);
 
+// The tables of a split fan-out (cz_plan_fanout_split) for runs already validated and seg_blocks >= 1:
+// `tiles` / `joins` must hold fanout_split_counts(...).ntiles / .njoins records.
+struct FanoutSplitCounts {
+    uint64_t ntiles, njoins, npart;
+};
+uint32_t fanout_split();  // publish runs of a full wave or more with payloads of at least this take the split fan-out (cz_tune "fanout_split")
+uint32_t fanout_split_seg_blocks(const cz_fanout_run *runs, uint32_t nruns);  // seg_blocks == 0
+FanoutSplitCounts fanout_split_counts(const cz_fanout_run *runs, uint32_t nruns, uint32_t seg_blocks);
+void plan_fanout_split(const cz_fanout_run *runs, uint32_t nruns, const void *d_in, uint32_t seg_blocks,
+                       cz_fanout_tile *tiles, uint32_t class_count[2], cz_fanout_join *joins);
+
 // segments, combine records and partial records the planner makes for one frame of `len` (payload for seal, body
 // for open) -- lets a caller size its buffers before planning
 inline void plan_counts(uint64_t len, int open, uint32_t seg_blocks, uint64_t &nseg, uint64_t &ncomb, uint64_t &npart)

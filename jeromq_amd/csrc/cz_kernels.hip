@@ -3262,6 +3262,119 @@ __global__ __launch_bounds__(BLOCK) void k_seal_combine(const cz_frame_desc *__r
         st16<false>(dst, tag[0], tag[1], tag[2], tag[3]);
 }
 
+// Split PUB fan-out (cz_seal_fanout_split): the lanes are (run, subscriber, segment).  Wave w of this
+// launch's slice of the tile table serves subscribers [first, first + 64) of run tiles[w].run on box
+// blocks [first_block, first_block + nblocks) of their bodies.  The wave index goes through
+// readfirstlane, so the tile and run records are scalar loads and payload, length, flags, block
+// range and chunk count are wave-uniform: only the key, the counter and the output are per lane,
+// and what seal_segments_body proves per wave by ballot holds here by construction.
+// ST_LINES: a full wave of a 16-byte aligned payload takes a line emitter, EmitSegLines where the
+// run's slots lie on 128-byte lines and EmitShiftLines (any byte offset) otherwise -- the choice
+// seal_segments_body makes.  ST_DIRECT: lane-wise.  The class is a performance choice only: a wave
+// of the line slice that is not full, or whose payload is off 16-byte alignment, stores lane-wise.
+// Both emitters clip their stores to the tile's own bytes, so the tiles of one body and the bodies
+// of neighbouring subscribers may share cache lines at any stride.  The tile that holds a body's
+// last block zeroes the rest of the slot where the run owns its slots (fanout_owns).
+// No workgroup barrier: the waves of a workgroup serve different runs and tiles.
+template <int ST>
+__global__ __launch_bounds__(BLOCK)
+__attribute__((amdgpu_waves_per_eu(ST == ST_LINES ? CZ_SEG_LINES_WAVES_PER_EU : 1,
+                                   ST == ST_LINES ? CZ_SEG_LINES_WAVES_PER_EU : 8))) void
+k_seal_fanout_tiles(const cz_fanout_run *__restrict__ runs, const cz_fanout_tile *__restrict__ tiles, uint32_t ntiles,
+                    const uint8_t *__restrict__ in, const cz_fanout_sub *__restrict__ subs,
+                    const uint8_t *__restrict__ subkeys, uint8_t *__restrict__ out, u32 *__restrict__ work)
+{
+    static_assert(ST == ST_LINES || ST == ST_DIRECT, "two staging classes");
+    extern __shared__ uint4 smem[];
+    const u32 w = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES + (threadIdx.x >> 6));
+    if (w >= ntiles)
+        return;
+    const cz_fanout_tile tl = tiles[w];
+    const cz_fanout_run r = runs[tl.run];
+    const u32 mlen = r.len + 33u;
+    const u32 nblk = (mlen + 63u) >> 6;
+    if (tl.first >= r.count || tl.first_block >= nblk || tl.nblocks == 0u)
+        return;
+    const u32 lane = threadIdx.x & 63u;
+    const bool full_wave = r.count - tl.first >= 64u;
+    const bool live = lane < r.count - tl.first;
+    const u32 i = tl.first + (live ? lane : 0u);
+    const u32 b0 = tl.first_block;
+    const u32 bend = tl.nblocks < nblk - b0 ? b0 + tl.nblocks : nblk;
+    const u32 total = seal_seg_bytes(mlen, b0, bend);
+    const u32 fl = r.flags & 0xffu;
+    const uint8_t *src = in + r.payload_off;
+    uint8_t *slot0 = out + r.out_off;
+    uint8_t *slot = slot0 + (uint64_t)i * r.out_stride;
+    uint8_t *dst = slot + 64ull * b0;
+    u32 *rec = tl.part == 0xffffffffu ? nullptr : work + 16ull * ((uint64_t)tl.part + (uint64_t)lane * tl.nseg);
+    const cz_fanout_sub sb = subs[(uint64_t)r.first_sub + i];
+    u32 key[8];
+    load_key(subkeys + 32ull * sb.key_idx, key);
+    const bool in_al = (((uintptr_t)src) & 15u) == 0;
+    bool done = false;
+    if constexpr (ST == ST_LINES) {
+        if (full_wave && in_al && total <= SHIFT_TOTAL_MAX) {
+            uint8_t *wl = reinterpret_cast<uint8_t *>(smem) + (threadIdx.x >> 6) * SHIFT_LDS_BYTES;
+            // (a segment that starts at an odd block is 64 bytes into its slot's line)
+            if (((((uintptr_t)slot0) | r.out_stride | (64u * b0)) & 127u) == 0) {
+                EmitSegLinesSeal em{reinterpret_cast<uint4 *>(wl), dst, lane, total, 0u, 0u};
+                em.init(b0 == 0);
+                seal_segment<true, EmitSegLinesSeal, true>(src, r.len, fl, sb.counter, key, b0, bend, rec, em);
+            } else {
+                EmitShiftLinesSeal em{wl, dst, lane, total, 0u, 0u};
+                em.init(b0 == 0);
+                seal_segment<true, EmitShiftLinesSeal, true>(src, r.len, fl, sb.counter, key, b0, bend, rec, em);
+            }
+            done = true;
+        }
+    }
+    if (!live)
+        return;
+    if (!done) {
+        if constexpr (ST == ST_LINES) {
+            // (a table planned for other addresses: correct, one path, not tuned)
+            EmitDirect<false> em{dst, total};
+            seal_segment<false>(per_lane_ptr(src), r.len, fl, sb.counter, key, b0, bend, rec, em);
+        } else if (in_al && aligned16(src, dst)) {
+            EmitDirect<true> em{dst, total};
+            seal_segment<true, EmitDirect<true>, true>(src, r.len, fl, sb.counter, key, b0, bend, rec, em);
+        } else if (in_al) {
+            EmitDirect<false> em{dst, total};
+            seal_segment<true, EmitDirect<false>, true>(src, r.len, fl, sb.counter, key, b0, bend, rec, em);
+        } else {
+            // a scalar load drops the low address bits: the payload off 16-byte alignment is read per lane
+            EmitDirect<false> em{dst, total};
+            seal_segment<false>(per_lane_ptr(src), r.len, fl, sb.counter, key, b0, bend, rec, em);
+        }
+    }
+    if (bend == nblk && r.out_stride > mlen && fanout_owns(r.out_stride))
+        zero_bytes(slot + mlen, (u32)(r.out_stride - mlen));
+}
+
+// The combine step of the split fan-out: one lane per (split run, subscriber).  Wave w's record gives
+// the run, the wave's first subscriber, lane 0's first partial record and the segments per body.
+__global__ __launch_bounds__(BLOCK) void k_fanout_join(const cz_fanout_run *__restrict__ runs,
+                                                        const cz_fanout_join *__restrict__ joins, uint32_t njoins,
+                                                        uint8_t *__restrict__ out, const u32 *__restrict__ work)
+{
+    const u32 w = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES + (threadIdx.x >> 6));
+    if (w >= njoins)
+        return;
+    const cz_fanout_join jn = joins[w];
+    const cz_fanout_run r = runs[jn.run];
+    const u32 lane = threadIdx.x & 63u;
+    if (jn.first >= r.count || lane >= r.count - jn.first || jn.nseg == 0u)
+        return;
+    u32 tag[4];
+    combine_tag(work + 16ull * ((uint64_t)jn.part + (uint64_t)lane * jn.nseg), jn.nseg, tag);
+    uint8_t *dst = out + r.out_off + (uint64_t)(jn.first + lane) * r.out_stride + 16;
+    if ((((uintptr_t)dst) & 15u) == 0)
+        st16<true>(dst, tag[0], tag[1], tag[2], tag[3]);
+    else
+        st16<false>(dst, tag[0], tag[1], tag[2], tag[3]);
+}
+
 __global__ __launch_bounds__(BLOCK) CZ_OPEN_SEG_OCC void k_open_segments(const cz_frame_desc *__restrict__ desc,
                                                           const cz_segment *__restrict__ segs, uint32_t nseg,
                                                           const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
@@ -4101,6 +4214,37 @@ hipError_t czk_seal_segments(const cz_frame_desc *desc, const cz_segment *segs, 
                            mode | (seal_segments_two_pass(g_knobs) ? SEGMODE_REST : 0));
     if (ncomb)
         hipLaunchKernelGGL(k_seal_combine, dim3((ncomb + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, desc, comb, ncomb,
+                           (uint8_t *)out, (const u32 *)work);
+    return hipGetLastError();
+}
+
+// Split PUB fan-out: the tile table holds class_count[CZ_FANOUT_TILE_LINES] waves for the line
+// emitters, then class_count[CZ_FANOUT_TILE_DIRECT] lane-wise ones; the join runs after both -- at
+// most three launches whatever the number of runs.
+hipError_t czk_seal_fanout_split(const cz_fanout_run *runs, const cz_fanout_tile *tiles, const uint32_t class_count[2],
+                                 const cz_fanout_join *joins, uint32_t njoins, const void *in,
+                                 const cz_fanout_sub *subs, const void *subkeys, void *out, void *work, hipStream_t s)
+{
+    static_assert(CZ_FANOUT_TILE_LINES == 0 && CZ_FANOUT_TILE_DIRECT == 1, "classes in table order");
+    uint32_t t0 = 0;
+    for (int cls = 0; cls < 2; t0 += class_count[cls++]) {
+        if (class_count[cls] == 0)
+            continue;
+        const Launch l = plan_fanout_tiles(cls, class_count[cls]);
+#define CZ_CASE(ST)                                                                                                   \
+    case ST:                                                                                                          \
+        hipLaunchKernelGGL(k_seal_fanout_tiles<ST>, dim3(l.grid), dim3(BLOCK), l.lds, s, runs, tiles + t0,            \
+                           class_count[cls], (const uint8_t *)in, subs, (const uint8_t *)subkeys, (uint8_t *)out,     \
+                           (u32 *)work);                                                                              \
+        break;
+        switch (l.st) {
+            CZ_CASE(ST_LINES) CZ_CASE(ST_DIRECT)
+        default: return hipErrorInvalidValue;
+        }
+#undef CZ_CASE
+    }
+    if (njoins)
+        hipLaunchKernelGGL(k_fanout_join, dim3((njoins + WAVES - 1) / WAVES), dim3(BLOCK), 0, s, runs, joins, njoins,
                            (uint8_t *)out, (const u32 *)work);
     return hipGetLastError();
 }

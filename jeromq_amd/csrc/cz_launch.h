@@ -30,6 +30,10 @@ hipError_t czk_seal_fanout_runs(const cz_fanout_run *runs, const cz_fanout_wave 
 // The staging class cz_plan_fanout gives the full waves of a run (CZ_FANOUT_LINES / _REGION /
 // _DIRECT): czk_seal_fanout's choice for that run alone.  Host code, no device call.
 int czk_fanout_class(uint64_t out_stride, uint32_t len, uint32_t count, int aligned);
+// split PUB fan-out: lanes are (run, subscriber, segment); tiles by class, then the join
+hipError_t czk_seal_fanout_split(const cz_fanout_run *runs, const cz_fanout_tile *tiles, const uint32_t class_count[2],
+                                 const cz_fanout_join *joins, uint32_t njoins, const void *in,
+                                 const cz_fanout_sub *subs, const void *subkeys, void *out, void *work, hipStream_t s);
 
 // descriptor and segmented (ragged) batches
 hipError_t czk_seal_desc(const cz_frame_desc *desc, const uint32_t *order, uint32_t count, const void *in, void *out,

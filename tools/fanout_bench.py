@@ -28,8 +28,12 @@ flush group in one call), see runs_rows and engine_runs_leg: R runs x N subscrib
 the 256 x publish flush with the frames in the segment plan, routed by fanout_min 64, and routed by
 fanout_short.
 
-Writes one JSON (default profiles/fanout/fanout.json, with --runs profiles/fanout/fanout_runs.json) and
-prints it."""
+--split measures the split fan-out (cz_plan_fanout_split + cz_seal_fanout_split: lanes are (run, subscriber,
+segment)), see split_rows and engine_split_leg: R runs x N subscribers x len on the device against the grouped
+call and the segment kernels, and the 256 x publish flush in the segment plan against fanout_split = len.
+
+Writes one JSON (default profiles/fanout/fanout.json, with --runs profiles/fanout/fanout_runs.json, with
+--split profiles/fanout/fanout_split.json) and prints it."""
 import argparse
 import ctypes
 import json
@@ -338,6 +342,180 @@ def fanout_short_rule(rows, engines):
     return verdict, best
 
 
+SPLIT_SHAPES = ((1, 64), (16, 64), (1, 1024), (16, 1024), (256, 1024))   # R x N
+SPLIT_LENS = (1024, 4096, 16384, 65536)
+
+
+def split_rows(args, torch, dev, batch, _lib):
+    """--split, device legs: R runs x N subscribers x len, laid out as runs_rows lays them out, same method:
+      (e)   one cz_seal_fanout_split call at the segment length a flush of that size picks (at most three launches);
+      (d)   one cz_seal_fanout_runs call;
+      (b')  the same R x N descriptors through cz_seal_segments at the same segment length, its host planning
+            (descriptors + cz_plan_segments) timed beside it, and the metadata bytes of (e) and (b')."""
+    L = _lib.lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    rows = []
+    for length in args.split_lens:
+        for nr, n in SPLIT_SHAPES:
+            stride = round_up(length + 33, 128)
+            pstride = round_up(length, 16) + 16
+            payload = torch.empty(nr * pstride + 256, dtype=torch.uint8, device=dev)
+            batch.fill(payload, 1)
+            sub = torch.empty(n * 32, dtype=torch.uint8, device=dev)
+            batch.fill(sub, 3)
+            sub = sub.view(n, 32)
+            out = torch.empty(nr * n * stride, dtype=torch.uint8, device=dev)
+            rng = np.random.default_rng(nr * n + length)
+            subs = np.zeros(nr * n, dtype=batch.FANOUT_SUB_DTYPE)
+            subs["counter"] = rng.integers(0, 1 << 63, size=nr * n, dtype=np.uint64)
+            subs["key_idx"] = np.tile(np.arange(n), nr)
+            d_subs = torch.from_numpy(subs.view(np.uint8).copy()).to(dev)
+            runs = np.zeros(nr, dtype=batch.FANOUT_RUN_DTYPE)
+            runs["payload_off"] = np.arange(nr, dtype=np.uint64) * np.uint64(pstride)
+            runs["out_off"] = np.arange(nr, dtype=np.uint64) * np.uint64(n * stride)
+            runs["out_stride"], runs["len"], runs["count"] = stride, length, n
+            runs["first_sub"] = np.arange(nr) * n
+            nblk = (length + 33 + 63) // 64
+            seg = engine_seg_blocks(nr * n * nblk, nblk)
+            t0 = time.perf_counter()
+            sp = batch.plan_fanout_split(runs, payload, out, seg)
+            t_split_plan = time.perf_counter() - t0
+            sp.to(dev)
+            work = torch.empty(64 * max(sp.npart, 1), dtype=torch.uint8, device=dev)
+            gp = batch.plan_fanout(runs, payload, out).to(dev)
+
+            def plan_segments():
+                desc = np.zeros(nr * n, dtype=batch.DESC_DTYPE)
+                desc["in_off"] = np.repeat(runs["payload_off"], n)
+                desc["out_off"] = np.arange(nr * n, dtype=np.uint64) * np.uint64(stride)
+                desc["len"], desc["prev"] = length, -1
+                desc["key_idx"], desc["counter"] = subs["key_idx"], subs["counter"]
+                return desc, batch.SegmentPlan(desc, seg_blocks=seg)
+
+            t_plan = []
+            for rep in range(3):
+                t0 = time.perf_counter()
+                desc, pl = plan_segments()
+                t_plan.append(time.perf_counter() - t0)
+            pl.to(dev)
+            d_desc = torch.from_numpy(desc.view(np.uint8)).to(dev)
+            # prepared ctypes calls: the wrappers' bounds checks cost more host time than a small launch takes
+            seal_split, seal_runs, seal_segs = L.cz_seal_fanout_split, L.cz_seal_fanout_runs, L.cz_seal_segments
+            split_args = (sp.d_runs.data_ptr(), nr, sp.d_tiles.data_ptr(), (ctypes.c_uint32 * 2)(*sp.class_count),
+                          sp.d_joins.data_ptr(), len(sp.joins), payload.data_ptr(), d_subs.data_ptr(), sub.data_ptr(),
+                          out.data_ptr(), work.data_ptr(), stream)
+            grouped_args = (gp.d_runs.data_ptr(), nr, gp.d_waves.data_ptr(), (ctypes.c_uint32 * 3)(*gp.class_count),
+                            gp.region_stride, payload.data_ptr(), d_subs.data_ptr(), sub.data_ptr(), out.data_ptr(), stream)
+            seg_args = (d_desc.data_ptr(), pl.d_seg.data_ptr(), pl.nseg, pl.d_comb.data_ptr(), pl.ncomb,
+                        payload.data_ptr(), out.data_ptr(), sub.data_ptr(), pl.d_work.data_ptr(), stream)
+
+            def call(f, a):
+                def go():
+                    if f(*a):
+                        raise RuntimeError(_lib.last_error())
+                return go
+
+            batch.seal_fanout_split(sp, payload, d_subs, sub, out, work=work)   # (the checked wrapper once: bounds)
+            legs = {"split": call(seal_split, split_args), "grouped": call(seal_runs, grouped_args),
+                    "segments_short": call(seal_segs, seg_args)}
+            # sanity at the timed shape: the three legs write the same bodies
+            legs["segments_short"]()
+            want = out.clone()
+            for k in ("split", "grouped"):
+                out.zero_()
+                legs[k]()
+                torch.cuda.synchronize()
+                assert torch.equal(want.view(nr * n, stride)[:, :length + 33], out.view(nr * n, stride)[:, :length + 33]), \
+                    f"{k} and cz_seal_segments disagree"
+            del want
+            inner = {}
+            for k, fn in legs.items():     # warm-up, and enough calls for a ~2 ms window
+                inner[k] = max(1, min(200, math.ceil(2.0 / max(event_ms(torch, fn, 1), 1e-3))))
+            times = {k: [] for k in legs}
+            for rep in range(args.reps):
+                for k, fn in legs.items():
+                    times[k].append(event_ms(torch, fn, inner[k]))
+            row = {"runs": nr, "n": n, "lanes": nr * n, "len": length, "out_stride": stride, "seg_blocks": seg,
+                   "tiles": len(sp.tiles), "tile_class_count": sp.class_count, "joins": len(sp.joins), "npart": sp.npart,
+                   "split_plan_host_ms": round(t_split_plan * 1e3, 4),
+                   "split_metadata_bytes": int(runs.nbytes + sp.tiles.nbytes + sp.joins.nbytes + subs.nbytes),
+                   "segments": pl.nseg, "combines": pl.ncomb,
+                   "segments_plan_host_ms": round(statistics.median(t_plan) * 1e3, 4),
+                   "segments_metadata_bytes": int(desc.nbytes + pl.segments.nbytes + pl.combines.nbytes)}
+            for k in legs:
+                med = statistics.median(times[k])
+                row[k + "_ms"] = round(med, 5)
+                row[k + "_all_ms"] = [round(t, 5) for t in times[k]]
+                row[k + "_calls_per_window"] = inner[k]
+            rows.append(row)
+            print(f"R={nr} n={n} len={length} seg={seg}: " + ", ".join(f"{k} {row[k + '_ms']} ms" for k in legs),
+                  file=sys.stderr)
+            del payload, sub, out, d_subs, d_desc, pl, sp, gp, work
+            torch.cuda.empty_cache()
+    return rows
+
+
+def engine_split_leg(args, _lib, length):
+    """--split, engine leg: --engine-msgs x publish of `length` bytes to --engine-conns connections, flushed with
+    the frames in the segment plan (fanout_split 0) and with fanout_split = length; wall clock of flush_out, one
+    warm-up round, legs interleaved."""
+    from jeromq_amd.engine import CurveBatchEngine
+    L = _lib.lib()
+    nc, nm = args.engine_conns, args.engine_msgs
+    body = length + 33
+    wire_bytes = nc * nm * (body + (9 if body > 255 else 2))
+    payloads = [np.random.default_rng(m).integers(0, 256, size=length, dtype=np.uint8).tobytes() for m in range(nm)]
+    eng = CurveBatchEngine(arena_bytes=nm * round_up(length, 16) + 4096)
+    cc = [eng.add_connection(np.random.default_rng(1000 + i).integers(0, 256, size=32, dtype=np.uint8).tobytes())
+          for i in range(nc)]
+    ids = (ctypes.c_int * nc)(*cc)
+    routings = {"segments": 0, "fanout_split": length}
+
+    def run(split):
+        old = L.cz_tune(b"fanout_split", split)
+        try:
+            for p in payloads:
+                _lib.check(L.cz_engine_publish(eng._h, ids, nc, p, length, 0, None), "cz_engine_publish")
+            t0 = time.perf_counter()
+            eng.flush_out()
+            return time.perf_counter() - t0
+        finally:
+            L.cz_tune(b"fanout_split", old)
+
+    res = {k: [] for k in routings}
+    for rep in range(args.reps + 1):
+        for k, split in routings.items():
+            t = run(split)
+            if rep:
+                res[k].append(t)
+    eng.close()
+    out = {"connections": nc, "messages": nm, "len": length, "wire_bytes": wire_bytes, "clock": "time.perf_counter"}
+    for k, v in res.items():
+        out[k + "_flush_ms"] = round(statistics.median(v) * 1e3, 3)
+        out[k + "_flush_all_ms"] = [round(t * 1e3, 3) for t in v]
+    print(f"engine len={length}: " + ", ".join(f"{k} {out[k + '_flush_ms']} ms" for k in routings), file=sys.stderr)
+    return out
+
+
+def fanout_split_rule(rows, engines):
+    """The rule that sets the shipped fanout_split, fixed before the run: the smallest measured length L such that,
+    for every measured length >= L, the split call is not slower than (b') in the median at every measured
+    R x N >= 1024 lanes and the flush routed by fanout_split is not slower than the segment-plan flush; 0 if no
+    length qualifies."""
+    verdict = {}
+    for length in sorted({r["len"] for r in rows}):
+        dev_ok = all(r["split_ms"] <= r["segments_short_ms"] for r in rows if r["len"] == length and r["lanes"] >= 1024)
+        eng = [e for e in engines if e["len"] == length]
+        eng_ok = bool(eng) and all(e["fanout_split_flush_ms"] <= e["segments_flush_ms"] for e in eng)
+        verdict[str(length)] = {"device": dev_ok, "engine": eng_ok if eng else None}
+    best = 0
+    for length in sorted((int(k) for k in verdict), reverse=True):
+        if not (verdict[str(length)]["device"] and verdict[str(length)]["engine"]):
+            break
+        best = length
+    return verdict, best
+
+
 def engine_leg(args, torch, _lib):
     from jeromq_amd.engine import CurveBatchEngine
     L = _lib.lib()
@@ -432,9 +610,14 @@ def main():
     ap.add_argument("--runs-n", type=int, nargs="*", default=list(RUNS_N))
     ap.add_argument("--runs-lens", type=int, nargs="*", default=list(RUNS_LENS))
     ap.add_argument("--engine-runs-lens", type=int, nargs="*", default=list(RUNS_LENS))
+    ap.add_argument("--split", action="store_true",
+                    help="the split fan-out instead: subscriber x segment grid (default --out: fanout_split.json)")
+    ap.add_argument("--split-lens", type=int, nargs="*", default=list(SPLIT_LENS))
+    ap.add_argument("--engine-split-lens", type=int, nargs="*", default=list(SPLIT_LENS))
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "fanout", "fanout_runs.json" if args.runs else "fanout.json")
+    args.out = args.out or os.path.join(ROOT, "profiles", "fanout", "fanout_split.json" if args.split else
+                                        "fanout_runs.json" if args.runs else "fanout.json")
     if args.reps < 5:
         ap.error("--reps must be at least 5")
     import torch
@@ -449,7 +632,33 @@ def main():
     out = {"device": torch.cuda.get_device_name(0), "library": _lib.lib().cz_version().decode(),
            "fanout_kernels_sha256": build.kernel_code_sha256(_lib.LIB_PATH, kernels), "reps": args.reps,
            "clock_device": "hipEvent (torch.cuda.Event), median", "ab_lib": args.ab_name or args.ab_lib}
-    if args.runs:
+
+    def write():
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+    if args.split:
+        out["fanout_runs_kernels_sha256"] = build.kernel_code_sha256(
+            _lib.LIB_PATH, [k.replace("k_seal_fanout<", "k_seal_fanout_runs<") for k in kernels])
+        out["fanout_split_kernels_sha256"] = build.kernel_code_sha256(
+            _lib.LIB_PATH, ["k_seal_fanout_tiles<1>", "k_seal_fanout_tiles<0>", "k_fanout_join"])
+        out["segment_kernels_sha256"] = build.kernel_code_sha256(
+            _lib.LIB_PATH, ["k_seal_segments_lines", "k_seal_segments", "k_seal_combine"])
+        out["fanout_split_default"] = _lib.lib().cz_tune(b"fanout_split", 0)
+        _lib.lib().cz_tune(b"fanout_split", out["fanout_split_default"])
+        if not args.no_device:
+            out["split_legs"] = split_rows(args, torch, dev, batch, _lib)
+            write()   # (kept if an engine leg below cannot get its buffers)
+        if not args.no_engine:
+            out["engine_split"] = []
+            for length in args.engine_split_lens:
+                out["engine_split"].append(engine_split_leg(args, _lib, length))
+                write()
+        if "split_legs" in out and "engine_split" in out:
+            out["fanout_split_verdict"], out["fanout_split_rule"] = fanout_split_rule(out["split_legs"], out["engine_split"])
+    elif args.runs:
         out["fanout_runs_kernels_sha256"] = build.kernel_code_sha256(
             _lib.LIB_PATH, [k.replace("k_seal_fanout<", "k_seal_fanout_runs<") for k in kernels])
         out["fanout_short_default"] = _lib.lib().cz_tune(b"fanout_short", 0)
@@ -462,12 +671,9 @@ def main():
             out["fanout_short_verdict"], out["fanout_short_rule"] = fanout_short_rule(out["runs_legs"], out["engine_runs"])
     elif not args.no_device:
         out["device_legs"] = device_rows(args, torch, dev, batch, _lib, ab)
-    if not args.no_engine and not args.runs:
+    if not args.no_engine and not args.runs and not args.split:
         out["engine"] = engine_leg(args, torch, _lib)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    write()
     print(json.dumps(out))
 
 
