@@ -369,6 +369,76 @@ int cz_seal_fanout_split(const cz_fanout_run *d_runs, uint32_t nruns, const cz_f
                          const void *d_in, const cz_fanout_sub *d_subs, const void *d_subkeys, void *d_out,
                          void *d_work, void *stream);
 
+/* ---- 3f. fan-in: same-size bodies of many connections opened in one call -----------------
+ * The mirror image of sections 3c and 3d: a collector in front of thousands of publishers, a ROUTER
+ * taking small requests, a SUB with many upstreams.  Every connection's StreamEngine runs
+ * mechanism.decode on each of its frames under its own key and cnPeerNonce (StreamEngine.decodeAndPush
+ * -> mechanism.decode, once per message and per connection: StreamEngine.java:1067-1098,
+ * CurveClientMechanism.java:166-224, CurveServerMechanism.java:165-225).  Here R runs of same-size
+ * bodies are one call of at most three launches whatever R: one lane per body, a 16-byte record per
+ * body instead of a 40-byte descriptor and a 16-byte segment, a per-wave record naming the run.
+ * Body j of a run lies at d_in + in_off + j * in_stride (`size` bytes), its payload goes to
+ * d_out + out_off + j * out_stride, and its record, status and nonce are d_subs / d_status / d_nonces
+ * [first_sub + j] (d_nonces optional).  Payload bytes, status (CZ_STATUS_* | flags << 8) and nonce
+ * are what cz_open_batch produces for the descriptor {in, out, size, key_idx, counter = the floor,
+ * CZ_DESC_CHECK_NONCE or not, prev = -1}; a bad tag zeroes the plaintext, and a frame rejected before
+ * decryption gets zeros over its payload bytes.
+ * CZ_FANIN_FLOOR_IS_BODY: `floor` is a byte offset into d_in, and the floor is the wire nonce (BE64
+ * at +8) of the body that starts there, accepted or not -- the connection's previous body, in this
+ * run, in another, or in no run at all.  That is what lets a chain cross run edges and reach bodies
+ * that stay in a segment plan, with a 16-byte record and no index space for `prev`.
+ * Output ownership per run by out_stride alone, the rule of cz_open_uniform: an owning stride gets
+ * zeros past each payload and over rejected frames' whole slots; any other stride leaves the bytes
+ * between payloads untouched.  The kernel writes its own zeros (no zero-pad launch).  The caller
+ * keeps the runs' output ranges and record ranges disjoint.  size < 33: every frame is COMMAND or
+ * MALFORMED and nothing but owned slots' zeros is written.
+ * A full wave's class is the staging cz_open_uniform's rule gives the run's out_stride and payload
+ * length when d_in + in_off, in_stride, d_out + out_off and out_stride are all 16-byte aligned
+ * (lane-wise otherwise); partial waves are lane-wise.  Waves are sorted by class, longest size first.
+ * The class only decides which launch a wave rides in: a wave re-checks its own run's alignment,
+ * stride limits and LDS partition and stores lane-wise when they do not fit, so a table planned for
+ * other addresses is slower, never wrong. */
+#define CZ_FANIN_CHECK_NONCE 0x1   /* enforce nonce > floor (signed, as CZ_DESC_CHECK_NONCE) */
+#define CZ_FANIN_FLOOR_IS_BODY 0x2 /* `floor` is a byte offset into d_in: the floor is the wire nonce
+                                      (BE64 at +8) of the body that starts there -- the connection's
+                                      previous body, in this run, in another, or in no run at all */
+typedef struct cz_fanin_sub {  /* 16 bytes, one per body */
+    uint64_t floor;    /* cnPeerNonce, or a body offset with CZ_FANIN_FLOOR_IS_BODY */
+    uint32_t key_idx;  /* subkey index */
+    uint32_t flags;    /* CZ_FANIN_* */
+} cz_fanin_sub;
+typedef struct cz_fanin_run {  /* 48 bytes */
+    uint64_t in_off, in_stride;   /* body j at d_in + in_off + j * in_stride, `size` bytes */
+    uint64_t out_off, out_stride; /* payload j at d_out + out_off + j * out_stride */
+    uint32_t size;                /* body bytes of every frame of the run */
+    uint32_t first_sub;           /* record, status and nonce index of body 0 */
+    uint32_t count;               /* 0 = the run contributes nothing */
+    uint32_t reserved;
+} cz_fanin_run;
+/* Host-side planner, no device call; d_in and d_out are used as addresses only (alignment class).
+ * Every run is validated before anything is written: size above 0x7fffffff, with count > 1 an
+ * out_stride below the payload length or an in_stride below size, first_sub + count past 2^32, an
+ * offset sum past the address space, null pointers -> CZ_EINVAL.  *nwaves = sum of ceil(count / 64); a
+ * wave_cap below that (or a null h_waves) returns CZ_EINVAL with *nwaves set and nothing else written,
+ * as cz_plan_fanout.  class_count[c] = waves of class c (CZ_FANOUT_LINES / _REGION / _DIRECT);
+ * *region_stride as cz_plan_fanout.
+ * Replaces StreamEngine.decodeAndPush -> mechanism.decode, once per message and per connection
+ * (StreamEngine.java:1067-1098, CurveClientMechanism.java:166-224, CurveServerMechanism.java:165-225). */
+int cz_plan_fanin(const cz_fanin_run *h_runs, uint32_t nruns, const void *d_in, const void *d_out,
+                  cz_fanout_wave *h_waves, uint32_t wave_cap, uint32_t *nwaves, uint32_t class_count[3],
+                  uint32_t *region_stride);
+/* StreamEngine.decodeAndPush -> mechanism.decode, once per message and per connection
+ * (StreamEngine.java:1067-1098, CurveClientMechanism.java:166-224, CurveServerMechanism.java:165-225):
+ * all of it for R runs, in at most three launches whatever R.  d_runs / d_waves: device copies of the
+ * run array and of the planner's wave table; class_count and region_stride as the planner returned
+ * them.  Asynchronous on `stream`; allocates nothing; can be captured into a graph.  nruns == 0 or no
+ * waves: CZ_OK, nothing launched.  Null pointers (d_nonces is optional): CZ_EINVAL, checked before the
+ * device is touched.  No device: CZ_EHIP; there is no CPU fallback. */
+int cz_open_fanin_runs(const cz_fanin_run *d_runs, uint32_t nruns, const cz_fanout_wave *d_waves,
+                       const uint32_t class_count[3], uint32_t region_stride, const void *d_in,
+                       const cz_fanin_sub *d_subs, const void *d_subkeys, void *d_out,
+                       uint16_t *d_status, uint64_t *d_nonces, void *stream);
+
 /* Synthetic data: fill d_buf with the counter-based SplitMix64 byte stream (seed). */
 int cz_fill(void *d_buf, uint64_t nbytes, uint64_t seed, void *stream);
 /* Measurement: device-to-device copy of nbytes (a multiple of 16) with 16-byte loads and stores,
@@ -546,8 +616,15 @@ int cz_engine_recv(cz_engine *e, int conn, const void *wire, uint64_t len);
  * the socket into it, then commit the bytes read.  Valid until the next engine call. */
 int cz_engine_recv_buffer(cz_engine *e, int conn, uint64_t min_bytes, uint8_t **buf, uint64_t *avail);
 int cz_engine_recv_commit(cz_engine *e, int conn, uint64_t n);
-/* parse, open and sequence-check every whole frame received on every connection */
+/* parse, open and sequence-check every whole frame received on every connection.  Inside a flush
+ * group (connection by connection, each connection's frames in order) a run of at least 64 consecutive
+ * frames of one body size whose payload is at most cz_tune("fanin_short") bytes leaves the segment plan,
+ * and all such runs of the group are one cz_open_fanin_runs call (section 3f); a run may span
+ * connection edges.  Delivered messages, cnPeerNonce, errors and events are those of the unrouted
+ * flush. */
 int cz_engine_flush_in(cz_engine *e);
+/* frames of the last cz_engine_flush_in that its cz_open_fanin_runs calls opened (0: nothing was routed) */
+uint64_t cz_engine_fanin_frames(const cz_engine *e);
 /* decoded messages of the last cz_engine_flush_in (pinned memory, valid until the next one) */
 int cz_engine_msgs_in(cz_engine *e, int conn, uint32_t *count);
 int cz_engine_msg_in(cz_engine *e, int conn, uint32_t i, const uint8_t **payload, uint32_t *len, int *msg_flags);
@@ -814,7 +891,15 @@ int cz_device_ok(void);
  *              every R x N >= 1024 (4 KiB: 0.0570 against 0.0612 ms for 16 publishes to 1024 subscribers; 64 KiB:
  *              0.542 against 0.558 ms; 1 KiB loses one shape, 0.1461 against 0.1460 ms at 2^18 lanes, so not 1024)
  *              and the routed flush of 256 publishes to 1024 connections is not slower than the segment-plan
- *              flush (4 KiB: 25.1 against 28.7 ms; 64 KiB: 305 against 307 ms); profiles/fanout/fanout_split.json */
+ *              flush (4 KiB: 25.1 against 28.7 ms; 64 KiB: 305 against 307 ms); profiles/fanout/fanout_split.json
+ *   "fanin_short": cz_engine_flush_in takes a run of at least 64 consecutive received frames (one full wave) of
+ *              one body size whose payload is at most this many bytes out of the segment plan; all such runs of a
+ *              flush group are opened by one cz_open_fanin_runs call (section 3f); 0 = rule off.  Default 100, the
+ *              largest measured length at which the fan-in call is not slower than cz_open_segments at every
+ *              R x N >= 1024 (100 B: 0.0104 against 0.0122 ms for 16 runs of 1024 bodies; 256 B: 0.0142 against
+ *              0.0151 ms; 1024 B: 0.0394 against 0.0304 ms, so not 1024) and the routed flush of 1024 connections x
+ *              16 frames is not slower than the unrouted one (100 B: 1.447 against 1.447 ms; 256 B: 1.567 against
+ *              1.554 ms, so not 256: such a flush is host- and copy-bound); profiles/fanin/fanin.json */
 int cz_tune(const char *key, int value);
 
 #ifdef __cplusplus

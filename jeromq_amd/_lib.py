@@ -116,6 +116,20 @@ assert ctypes.sizeof(cz_fanout_tile) == 24 and ctypes.sizeof(cz_fanout_join) == 
 CZ_FANOUT_TILE_LINES, CZ_FANOUT_TILE_DIRECT = 0, 1
 
 
+class cz_fanin_sub(ctypes.Structure):
+    _fields_ = [("floor", ctypes.c_uint64), ("key_idx", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class cz_fanin_run(ctypes.Structure):
+    _fields_ = [("in_off", ctypes.c_uint64), ("in_stride", ctypes.c_uint64), ("out_off", ctypes.c_uint64),
+                ("out_stride", ctypes.c_uint64), ("size", ctypes.c_uint32), ("first_sub", ctypes.c_uint32),
+                ("count", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(cz_fanin_sub) == 16 and ctypes.sizeof(cz_fanin_run) == 48
+CZ_FANIN_CHECK_NONCE, CZ_FANIN_FLOOR_IS_BODY = 1, 2
+
+
 class cz_accept_result(ctypes.Structure):
     _fields_ = [("rc", ctypes.c_int32), ("event", ctypes.c_int32), ("slot", ctypes.c_int32),
                 ("reply_len", ctypes.c_uint32)]
@@ -147,6 +161,9 @@ SIGNATURES = {
     "cz_plan_fanout_split": (_I, [_VP, _U32, _VP, _U32, _VP, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32), _VP,
                                   _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
     "cz_seal_fanout_split": (_I, [_VP, _U32, _VP, ctypes.POINTER(_U32), _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "cz_plan_fanin": (_I, [_VP, _U32, _VP, _VP, _VP, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32),
+                           ctypes.POINTER(_U32)]),
+    "cz_open_fanin_runs": (_I, [_VP, _U32, _VP, ctypes.POINTER(_U32), _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "cz_plan_order": (_I, [_VP, _U32, _VP]),
     "cz_plan_segments": (_I, [_VP, _U32, _I, _U32, _VP, _U32, ctypes.POINTER(_U32), _VP, _U32,
                               ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
@@ -195,6 +212,7 @@ SIGNATURES = {
     "cz_engine_conn_error": (_I, [_VP, _I, ctypes.POINTER(_I)]),
     "cz_engine_nonce": (_U64, [_VP, _I]),
     "cz_engine_peer_nonce": (_U64, [_VP, _I]),
+    "cz_engine_fanin_frames": (_U64, [_VP]),
     "cz_scalarmult": (_I, [_VP, _VP, _VP]),
     "cz_box_keypair": (_I, [_VP, _VP]),
     "cz_box_beforenm": (_I, [_VP, _VP, _VP]),

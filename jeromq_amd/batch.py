@@ -156,6 +156,76 @@ def seal_fanout_runs(plan, inp, subs, subkeys_t, out, stream=None):
                                               _stream(stream)), "cz_seal_fanout_runs")
 
 
+FANIN_SUB_DTYPE = np.dtype([("floor", "<u8"), ("key_idx", "<u4"), ("flags", "<u4")])
+FANIN_RUN_DTYPE = np.dtype([("in_off", "<u8"), ("in_stride", "<u8"), ("out_off", "<u8"), ("out_stride", "<u8"),
+                            ("size", "<u4"), ("first_sub", "<u4"), ("count", "<u4"), ("reserved", "<u4")])
+FANIN_CHECK_NONCE, FANIN_FLOOR_IS_BODY = _lib.CZ_FANIN_CHECK_NONCE, _lib.CZ_FANIN_FLOOR_IS_BODY
+
+
+class FaninPlan(FanoutPlan):
+    """Host plan of a fan-in open (cz_plan_fanin): the runs (FANIN_RUN_DTYPE) and, as FanoutPlan, `waves`
+    sorted by staging class, `class_count` and `region_stride`.  `to(device)` uploads the run and wave
+    tables.  A caller may replace `waves` and `class_count` with a table of its own before `to`."""
+
+
+def plan_fanin(runs_np, inp, out):
+    """Plan the fan-in open of `runs_np` (FANIN_RUN_DTYPE) reading `inp` and writing `out`: device tensors
+    (or plain addresses), used for their 16-byte alignment only.  Returns a FaninPlan."""
+    r = np.ascontiguousarray(runs_np, dtype=FANIN_RUN_DTYPE)
+    a_in, a_out = (t if isinstance(t, int) else t.data_ptr() for t in (inp, out))
+    nw, rs, cc = ctypes.c_uint32(), ctypes.c_uint32(), (ctypes.c_uint32 * 3)()
+    L = _lib.lib()
+    L.cz_plan_fanin(r.ctypes.data, len(r), a_in, a_out, None, 0, ctypes.byref(nw), cc, ctypes.byref(rs))
+    waves = np.zeros(max(nw.value, 1), dtype=FANOUT_WAVE_DTYPE)
+    _lib.check(L.cz_plan_fanin(r.ctypes.data, len(r), a_in, a_out, waves.ctypes.data, len(waves), ctypes.byref(nw),
+                               cc, ctypes.byref(rs)), "cz_plan_fanin")
+    return FaninPlan(r, waves[:nw.value], cc, rs.value)
+
+
+def _check_fanin_bounds(runs_np, inp, out, subs_np, nsubs, status, nonces):
+    """Every live run's bodies, output range (whole slots where the run owns them) and record, status and
+    nonce ranges inside their tensors; with the host copy of the records (`subs_np`), every
+    FLOOR_IS_BODY offset's 16 bytes inside `inp`."""
+    live = runs_np[runs_np["count"] > 0]
+    if len(live):
+        sz, cnt = live["size"].astype(np.uint64), live["count"].astype(np.uint64)
+        nout = np.where(sz >= 33, sz - np.uint64(33), 0).astype(np.uint64)
+        st = live["out_stride"]
+        owns = ((st % 128 == 0) & (st < (1 << 25))) | ((st % 16 == 0) & (st <= 256))   # whole slots are written
+        last = np.where(owns, st, nout)
+        end = live["first_sub"].astype(np.uint64) + cnt
+        if (np.any(live["in_off"] + (cnt - np.uint64(1)) * live["in_stride"] + sz > np.uint64(inp.numel()))
+                or np.any(live["out_off"] + (cnt - np.uint64(1)) * st + last > np.uint64(out.numel()))
+                or np.any(end > np.uint64(nsubs)) or np.any(end > np.uint64(status.numel()))
+                or (nonces is not None and np.any(end > np.uint64(nonces.numel())))):
+            raise ValueError("run out of bounds")
+    if subs_np is not None and len(subs_np):
+        body = (subs_np["flags"] & FANIN_FLOOR_IS_BODY) != 0
+        if np.any(subs_np["floor"][body] > np.uint64(max(inp.numel(), 16) - 16)) or (body.any() and inp.numel() < 16):
+            raise ValueError("FLOOR_IS_BODY offset out of bounds")
+
+
+def open_fanin_runs(plan, inp, subs, subkeys_t, out, status, nonces=None, stream=None, subs_np=None):
+    """Fan-in open: every run of `plan` (plan_fanin(...).to(device)) opened in one call of at most three
+    launches, one lane per body.  subs: a device tensor of 16-byte cz_fanin_sub records (FANIN_SUB_DTYPE);
+    body j of a run uses record, status (int16 / uint16 tensor) and nonce (int64 tensor, optional)
+    first_sub + j.  Bounds are checked against the plan's host copy of the runs and, when given, the host
+    copy of the records (`subs_np`: FLOOR_IS_BODY offsets)."""
+    _need_cuda_u8(inp, "in")
+    _need_cuda_u8(out, "out")
+    _need_cuda_u8(subkeys_t, "subkeys")
+    if subs is None or not subs.is_cuda or status is None or not status.is_cuda:
+        raise ValueError("subs and status must be CUDA (HIP) tensors")
+    if plan.nruns and plan.d_runs is None:
+        raise ValueError("plan not uploaded: plan.to(device)")
+    _check_fanin_bounds(plan.runs, inp, out, subs_np, subs.numel() * subs.element_size() // FANIN_SUB_DTYPE.itemsize,
+                        status, nonces)
+    cc = (ctypes.c_uint32 * 3)(*plan.class_count)
+    _lib.check(_lib.lib().cz_open_fanin_runs(_ptr(plan.d_runs), plan.nruns, _ptr(plan.d_waves), cc, plan.region_stride,
+                                             _ptr(inp), _ptr(subs), _ptr(subkeys_t), _ptr(out), _ptr(status),
+                                             _ptr(nonces), _stream(stream)), "cz_open_fanin_runs")
+
+
 FANOUT_TILE_DTYPE = np.dtype([("run", "<u4"), ("first", "<u4"), ("first_block", "<u4"), ("nblocks", "<u4"),
                               ("part", "<u4"), ("nseg", "<u4")])
 FANOUT_JOIN_DTYPE = np.dtype([("run", "<u4"), ("first", "<u4"), ("part", "<u4"), ("nseg", "<u4")])

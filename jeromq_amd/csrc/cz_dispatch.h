@@ -82,7 +82,7 @@ struct Knobs {
 };
 
 // ---- what a launcher launches -----------------------------------------------
-enum Family { K_SEAL_UNIFORM, K_SEAL_UNIFORM_INA, K_SEAL_FANOUT, K_OPEN_UNIFORM, K_OPEN_UNIFORM_CARRY, K_SEAL_FANOUT_TILES };
+enum Family { K_SEAL_UNIFORM, K_SEAL_UNIFORM_INA, K_SEAL_FANOUT, K_OPEN_UNIFORM, K_OPEN_UNIFORM_CARRY, K_SEAL_FANOUT_TILES, K_OPEN_FANIN };
 constexpr int64_t PAD_NONE = -1;
 
 struct Launch {
@@ -230,6 +230,23 @@ inline Launch plan_fanout_runs(int cls, uint32_t nwaves, uint32_t part16)
     const int st = cls == CZ_FANOUT_LINES ? ST_LINES : (cls == CZ_FANOUT_REGION ? ST_REGION : ST_DIRECT);
     return Launch{K_SEAL_FANOUT, st, st != ST_REGION, 16, MODE_ZMQ, (nwaves + WAVES - 1) / WAVES,
                   st == ST_REGION ? (uint32_t)(WAVES * 16u * part16) : staging_lds(st, 0, true), PAD_NONE};
+}
+
+// czk_open_fanin_runs: the staging class of a run's full waves in cz_plan_fanin's wave table -- what
+// pick_staging gives its plaintext slots when body base, in_stride, output base and out_stride are all
+// on 16 bytes (`aligned`); a run without a full wave is lane-wise
+inline int plan_fanin_class(uint64_t out_stride, uint32_t size, uint32_t count, bool aligned)
+{
+    const int st = count >= 64u ? pick_staging(out_stride, size >= 33u ? size - 33u : 0u, aligned) : (int)ST_DIRECT;
+    return st == ST_LINES ? CZ_FANOUT_LINES : st == ST_REGION ? CZ_FANOUT_REGION : CZ_FANOUT_DIRECT;
+}
+// ... and the launch of one class's slice of the wave table (`nwaves` waves, one per 64 lanes): the
+// emitters and whole-line loads of k_open_uniform's same class, the region partition of plan_fanout_runs
+inline Launch plan_fanin_runs(int cls, uint32_t nwaves, uint32_t part16)
+{
+    const int st = cls == CZ_FANOUT_LINES ? ST_LINES : (cls == CZ_FANOUT_REGION ? ST_REGION : ST_DIRECT);
+    return Launch{K_OPEN_FANIN, st, st != ST_REGION, 16, MODE_ZMQ, (nwaves + WAVES - 1) / WAVES,
+                  st == ST_REGION ? (uint32_t)(WAVES * 16u * part16) : staging_lds(st, 0, false), PAD_NONE};
 }
 
 // czk_seal_fanout_split: one class's slice of the tile table, one wave per tile; the line class stages

@@ -266,6 +266,7 @@ struct cz_engine {
         d_fruns, d_fwaves,  // grouped fan-out: run and wave tables
         d_ftiles, d_fjoins, d_fwork;  // split fan-out: tile and join tables, partial records
     uint32_t pub_seq = 0;  // id of the last cz_engine_publish call (OutMsg::pub)
+    uint64_t fanin_frames = 0;  // frames of the last flush_in that its cz_open_fanin_runs calls opened
     HostBuf h_status, h_nonces;
     HostBuf h_meta;  // pinned staging of descriptors / items / segment lists (async H2D)
     RxPool rxpool;   // every connection's receive buffer
@@ -628,6 +629,7 @@ struct cz_engine {
     {
         PhaseTimer pt("flush_in");
         in_msgs.clear();
+        fanin_frames = 0;
         for (Conn &c : conns)
             c.in_msgs.clear();
         // 0. the live connections, in groups of ~equal received bytes
@@ -748,8 +750,21 @@ struct cz_engine {
             uint64_t nseg = 0, ncomb = 0, npart = 0;
             uint64_t b0 = 0, soff = 0, coff = 0, woff = 0;  // where its arrays start
             bool bad_plan = false;
+            // fan-in: maximal runs of consecutive frames of one body size (group-relative first frame),
+            // at least one full wave of them with a payload of at most cz_tune("fanin_short") bytes.
+            // Their body and plaintext slots are contiguous at one stride each, so a run is one
+            // cz_fanin_run of the group's cz_open_fanin_runs call and leaves the segment plan; it may
+            // span connection edges.  routed[i]: frame i is in such a run.
+            std::vector<std::pair<uint32_t, uint32_t>> runs;  // (first, count)
+            std::vector<uint8_t> routed;
+            uint64_t nfwave = 0, nrouted = 0;
+            // its fan-in block in the metadata staging and in d_subs: records by group-relative frame index,
+            // then the run table, then the wave table -- one upload
+            uint64_t foff = 0, fbytes = 0;
+            uint32_t fclass[3] = {0, 0, 0}, fregion = 0;
         };
         std::vector<GroupWork> gw(groups.size());
+        const uint32_t fin_short = fanin_short();
         auto parse = [&](size_t gi) {
             GroupWork &w = gw[gi];
             const Group &g = groups[gi];
@@ -779,11 +794,29 @@ struct cz_engine {
                 p.consumed = consumed;
                 p.perr = prc == CZ_OK ? 0 : prc;
             }
-            for (const cz_v2_frame &f : w.frames) {
+            const uint32_t gn = (uint32_t)w.frames.size();
+            for (uint32_t i = 0; fin_short && i < gn;) {
+                uint32_t j = i + 1;
+                while (j < gn && w.frames[j].size == w.frames[i].size)
+                    j++;
+                if (j - i >= 64u && w.frames[i].size >= CZ_MESSAGE_OVERHEAD &&
+                    w.frames[i].size - CZ_MESSAGE_OVERHEAD <= fin_short) {
+                    if (w.routed.empty())
+                        w.routed.assign(gn, 0);
+                    std::fill(w.routed.begin() + i, w.routed.begin() + j, (uint8_t)1);
+                    w.runs.push_back({i, j - i});
+                    w.nfwave += ((uint64_t)(j - i) + 63) / 64;
+                    w.nrouted += j - i;
+                }
+                i = j;
+            }
+            for (uint32_t i = 0; i < gn; i++) {
+                const cz_v2_frame &f = w.frames[i];
                 const uint64_t plen = f.size > CZ_MESSAGE_OVERHEAD ? f.size - CZ_MESSAGE_OVERHEAD : 0;
                 w.bslot += round_up(std::max<uint64_t>(f.size, 1), SLOT_ALIGN);
                 w.pslot += round_up(std::max<uint64_t>(plen, 1), SLOT_ALIGN);
-                plan_counts(f.size, 1, seg, w.nseg, w.ncomb, w.npart);
+                if (w.routed.empty() || !w.routed[i])  // (the routed frames get no segments)
+                    plan_counts(f.size, 1, seg, w.nseg, w.ncomb, w.npart);
             }
         };
         {
@@ -799,10 +832,16 @@ struct cz_engine {
         // 2. place the groups: absolute frame indices, slot offsets, segment-list offsets; size
         //    every buffer once
         uint32_t n = 0;
-        uint64_t bslot = 0, pslot = 0, nseg = 0, ncomb = 0, npart = 0;
+        uint64_t bslot = 0, pslot = 0, nseg = 0, ncomb = 0, npart = 0, nfan = 0;
         for (size_t gi = 0; gi < groups.size(); gi++) {
             Group &g = groups[gi];
             GroupWork &w = gw[gi];
+            w.foff = nfan;
+            if (!w.runs.empty())
+                w.fbytes = w.frames.size() * sizeof(cz_fanin_sub) + w.runs.size() * sizeof(cz_fanin_run) +
+                           w.nfwave * sizeof(cz_fanout_wave);
+            nfan += w.fbytes;
+            fanin_frames += w.nrouted;
             g.fa = n;
             for (size_t q = g.pa; q < g.pb; q++)
                 parsed[q].first += n;
@@ -822,7 +861,8 @@ struct cz_engine {
         }
         const uint64_t m_items = 0, m_desc = (uint64_t)n * sizeof(cz_v2_item),
                        m_seg = m_desc + (uint64_t)n * sizeof(cz_frame_desc),
-                       m_comb = m_seg + nseg * sizeof(cz_segment), m_end = m_comb + ncomb * sizeof(cz_combine);
+                       m_comb = m_seg + nseg * sizeof(cz_segment), m_fanin = m_comb + ncomb * sizeof(cz_combine),
+                       m_end = m_fanin + nfan;
         // (a device buffer that has to grow is reallocated here, which waits for the copies in
         //  flight; steady-state flushes reuse their buffers)
         if (n && ((e = d_in.reserve(bslot)) != hipSuccess || (e = d_plain.reserve(pslot)) != hipSuccess ||
@@ -833,6 +873,8 @@ struct cz_engine {
                   (e = d_seg.reserve(std::max<uint64_t>(nseg, 1) * sizeof(cz_segment))) != hipSuccess ||
                   (e = d_comb.reserve(std::max<uint64_t>(ncomb, 1) * sizeof(cz_combine))) != hipSuccess ||
                   (e = d_work.reserve(std::max<uint64_t>(npart, 1) * 64)) != hipSuccess ||
+                  // (the fan-out records' buffer of flush_out, which never runs beside flush_in)
+                  (nfan && (e = d_subs.reserve(nfan)) != hipSuccess) ||
                   (e = h_plain.reserve(pslot)) != hipSuccess || (e = h_status.reserve((uint64_t)n * 2)) != hipSuccess ||
                   (e = h_nonces.reserve((uint64_t)n * 8)) != hipSuccess || (e = h_meta.reserve(m_end)) != hipSuccess))
             return hip_fail(e, "cz_engine: alloc");
@@ -843,6 +885,7 @@ struct cz_engine {
         cz_frame_desc *h_desc = (cz_frame_desc *)(hm + m_desc);
         cz_segment *h_seg = (cz_segment *)(hm + m_seg);
         cz_combine *h_comb = (cz_combine *)(hm + m_comb);
+        uint8_t *h_fanin = hm + m_fanin;
         pt.mark("place");
         // 3. per group, on its own host thread: descriptors -- bodies unpacked into aligned slots,
         //    each connection's frames chained by prev (group-relative indices, as the kernels get
@@ -869,7 +912,53 @@ struct cz_engine {
                 }
             }
             const uint32_t gn = g.fb - g.fa;
-            plan_segments(desc, gn, 1, seg, w.sg.seg, w.sg.comb, w.sg.npart);
+            if (w.runs.empty()) {
+                plan_segments(desc, gn, 1, seg, w.sg.seg, w.sg.comb, w.sg.npart);
+            } else {
+                // Fan-in records of the routed frames, at the frame's index in the group (where its
+                // status and nonce land): a connection's first frame checks against cnPeerNonce,
+                // every later one against the wire nonce of its previous body's slot -- routed or
+                // not.  The descriptors above stay whole: the prev chains of the frames left in the
+                // segment plan resolve through them, and the delivery step reads them.
+                cz_fanin_sub *h_isubs = (cz_fanin_sub *)(h_fanin + w.foff);
+                cz_fanin_run *hr = (cz_fanin_run *)(h_isubs + gn);
+                cz_fanout_wave *hw = (cz_fanout_wave *)(hr + w.runs.size());
+                for (size_t q = g.pa; q < g.pb; q++) {
+                    const Parsed &p = parsed[q];
+                    const Conn &c = conns[p.conn];
+                    for (uint32_t k = 0; k < p.count; k++) {
+                        const uint32_t i = p.first - g.fa + k;
+                        if (!w.routed[i])
+                            continue;
+                        h_isubs[i] = k ? cz_fanin_sub{desc[i - 1].in_off, c.rx_key,
+                                                             CZ_FANIN_CHECK_NONCE | CZ_FANIN_FLOOR_IS_BODY}
+                                              : cz_fanin_sub{c.peer_nonce, c.rx_key, CZ_FANIN_CHECK_NONCE};
+                    }
+                }
+                for (size_t r = 0; r < w.runs.size(); r++) {
+                    const uint32_t first = w.runs[r].first, size = desc[first].len;
+                    hr[r] = {desc[first].in_off, round_up(size, SLOT_ALIGN), desc[first].out_off,
+                             round_up(std::max<uint64_t>(size - CZ_MESSAGE_OVERHEAD, 1), SLOT_ALIGN), size, first,
+                             w.runs[r].second, 0u};
+                }
+                w.fregion = plan_fanin(hr, (uint32_t)w.runs.size(), d_in.ptr, d_plain.ptr, hw, w.fclass);
+                // the segment plan of the frames that stay: planned over a packed copy of their
+                // descriptors, then named by their index in the whole array
+                std::vector<cz_frame_desc> rest;
+                std::vector<uint32_t> index;
+                rest.reserve(gn - w.nrouted);
+                index.reserve(gn - w.nrouted);
+                for (uint32_t i = 0; i < gn; i++)
+                    if (!w.routed[i]) {
+                        rest.push_back(desc[i]);
+                        index.push_back(i);
+                    }
+                plan_segments(rest.data(), (uint32_t)rest.size(), 1, seg, w.sg.seg, w.sg.comb, w.sg.npart);
+                for (cz_segment &sgm : w.sg.seg)
+                    sgm.frame = index[sgm.frame];
+                for (cz_combine &cb : w.sg.comb)
+                    cb.frame = index[cb.frame];
+            }
             w.sg.nseg = (uint32_t)w.sg.seg.size();
             w.sg.ncomb = (uint32_t)w.sg.comb.size();
             if (w.sg.nseg != w.nseg || w.sg.ncomb != w.ncomb || w.sg.npart != w.npart) {
@@ -888,6 +977,12 @@ struct cz_engine {
             cz_frame_desc *dd = (cz_frame_desc *)d_desc.ptr + g.fa;
             cz_segment *dsg = (cz_segment *)d_seg.ptr + w.soff;
             cz_combine *dcb = (cz_combine *)d_comb.ptr + w.coff;
+            const uint32_t nr = (uint32_t)w.runs.size();
+            // the group's fan-in block on the device: records, runs, waves, laid out as in the staging
+            const cz_fanin_sub *dis = (const cz_fanin_sub *)((const uint8_t *)d_subs.ptr + w.foff);
+            const cz_fanin_run *dir = (const cz_fanin_run *)(dis + gn);
+            const cz_fanout_wave *diw = (const cz_fanout_wave *)(dir + nr);
+            const uint64_t sub_a = nr ? (uint64_t)w.runs.front().first * sizeof(cz_fanin_sub) : 0u;  // first record used
             hipError_t r;
             // (a) metadata stream: the group's descriptors / items / segment lists
             if ((r = hipMemcpyAsync((cz_v2_item *)d_items.ptr + g.fa, h_items + g.fa, (uint64_t)gn * sizeof(cz_v2_item),
@@ -898,6 +993,9 @@ struct cz_engine {
                                                   hipMemcpyHostToDevice, qm)) != hipSuccess) ||
                 (w.sg.ncomb && (r = hipMemcpyAsync(dcb, h_comb + w.coff, (uint64_t)w.sg.ncomb * sizeof(cz_combine),
                                                    hipMemcpyHostToDevice, qm)) != hipSuccess) ||
+                // (one copy for the group's fan-in block, from the first routed frame's record on)
+                (nr && (r = hipMemcpyAsync((uint8_t *)d_subs.ptr + w.foff + sub_a, h_fanin + w.foff + sub_a,
+                                           w.fbytes - sub_a, hipMemcpyHostToDevice, qm)) != hipSuccess) ||
                 (qm != qk && (r = hipEventRecord(evm[gi], qm)) != hipSuccess))
                 return r;
             // (b) compute stream: once the group's bytes and metadata landed, unpack + open;
@@ -905,9 +1003,15 @@ struct cz_engine {
             if ((qh != qk && (r = hipStreamWaitEvent(qk, ev[gi], 0)) != hipSuccess) ||
                 (qm != qk && (r = hipStreamWaitEvent(qk, evm[gi], 0)) != hipSuccess) ||
                 (r = czk_v2_copy((const cz_v2_item *)d_items.ptr + g.fa, gn, d_wire.ptr, d_in.ptr, qk)) != hipSuccess ||
-                (r = czk_open_segments(dd, dsg, w.sg.nseg, dcb, w.sg.ncomb, d_in.ptr, d_plain.ptr, subkeys.ptr,
-                                       (uint8_t *)d_work.ptr + 64 * w.woff, (uint16_t *)d_status.ptr + g.fa,
-                                       (uint64_t *)d_nonces.ptr + g.fa, qk)) != hipSuccess ||
+                // the group's fan-in runs in one call (records, statuses and nonces by frame index in the
+                // group), then the segment plan of the frames that stay
+                (nr && (r = czk_open_fanin_runs(dir, diw, w.fclass, w.fregion, d_in.ptr, dis, subkeys.ptr, d_plain.ptr,
+                                                (uint16_t *)d_status.ptr + g.fa, (uint64_t *)d_nonces.ptr + g.fa,
+                                                qk)) != hipSuccess) ||
+                (w.sg.nseg &&
+                 (r = czk_open_segments(dd, dsg, w.sg.nseg, dcb, w.sg.ncomb, d_in.ptr, d_plain.ptr, subkeys.ptr,
+                                        (uint8_t *)d_work.ptr + 64 * w.woff, (uint16_t *)d_status.ptr + g.fa,
+                                        (uint64_t *)d_nonces.ptr + g.fa, qk)) != hipSuccess) ||
                 (qo != qk && ((r = hipEventRecord(evk[gi], qk)) != hipSuccess ||
                               (r = hipStreamWaitEvent(qo, evk[gi], 0)) != hipSuccess)) ||
                 (r = hipMemcpyAsync((uint8_t *)h_plain.ptr + g.pl0, (uint8_t *)d_plain.ptr + g.pl0, g.pl1 - g.pl0,
@@ -1536,5 +1640,7 @@ uint64_t cz_engine_peer_nonce(cz_engine *e, int conn)
     Conn *c = e ? e->conn(conn) : nullptr;
     return c ? c->peer_nonce : 0;
 }
+
+uint64_t cz_engine_fanin_frames(const cz_engine *e) { return e ? e->fanin_frames : 0; }
 
 }  // extern "C"

@@ -283,6 +283,25 @@ static std::atomic<uint64_t> g_fanout_split{4096};
 
 uint32_t fanout_split() { return (uint32_t)g_fanout_split.load(std::memory_order_relaxed); }
 
+// cz_engine_flush_in: a run of at least 64 consecutive received frames (one full wave) of one body size
+// whose payload is at most this many bytes leaves the segment plan for the flush group's one
+// cz_open_fanin_runs call; 0 = rule off (cz_tune "fanin_short").
+// Default 100, by the rule that set fanout_short: the largest measured length (of 100, 256, 1024, 4096) at which
+// the fan-in call (a) is not slower than cz_open_segments at the flush's own segment length (b) in the median at
+// every measured R x N >= 1024, and the flush routed by it is not slower than the unrouted flush
+// (tools/fanin_bench.py, profiles/fanin/fanin.json, medians of 7, legs interleaved):
+//   len   (a) / (b) ms at R x N = 1024, 16 384, 262 144               1024 connections x 16 frames, flush_in ms
+//   100   0.0098 / 0.0114   0.0104 / 0.0122   0.0354 / 0.0444         1.447 routed, 1.447 unrouted
+//   256   0.0133 / 0.0144   0.0142 / 0.0151   0.0502 / 0.0550         1.567 routed, 1.554 unrouted (so not 256)
+//   1024  0.0370 / 0.0227   0.0394 / 0.0304   0.1546 / 0.1595  (loses below 2^18 lanes; flush 2.155 / 2.967)
+//   4096  0.1305 / 0.0299   0.1330 / 0.0611   0.5846 / 0.6036  (loses below 2^18 lanes; flush 5.284 / 6.295)
+// The device gain at 100 and 256 B does not show in the flush: 16 384 small frames are a host- and copy-bound
+// flush (a tie at 100 B, +0.013 ms at 256 B).  Above a few blocks one lane per body is held to that lane's serial
+// walk, as on the send side.
+static std::atomic<uint64_t> g_fanin_short{100};
+
+uint32_t fanin_short() { return (uint32_t)g_fanin_short.load(std::memory_order_relaxed); }
+
 // NaCl box/open of one message on the device.  A MESSAGE is the NaCl box of
 // 0^32 || flags || payload, so m[32] rides as the flags byte and m[33:] as the payload; for open
 // the 16 bytes ahead of the tag are rebuilt as "\x07MESSAGE" || n[16:24] and the nonce check is off.
@@ -522,6 +541,46 @@ uint32_t plan_fanout(const cz_fanout_run *runs, uint32_t nruns, const void *d_in
     return region_stride;
 }
 
+uint64_t fanin_waves(const cz_fanin_run *runs, uint32_t nruns)
+{
+    uint64_t n = 0;
+    for (uint32_t r = 0; r < nruns; r++)
+        n += ((uint64_t)runs[r].count + 63) / 64;
+    return n;
+}
+
+// Fan-in open: the wave table of plan_fanout for runs of received bodies.  A full wave takes its run's
+// staging class (czk_fanin_class: pick_staging for the run's plaintext slots with body base, in_stride,
+// output base and out_stride all on 16 bytes), a partial last wave opens lane-wise.  Waves sorted by
+// class, then longest body first (stable: run order, then wave order).
+uint32_t plan_fanin(const cz_fanin_run *runs, uint32_t nruns, const void *d_in, const void *d_out, cz_fanout_wave *waves,
+                    uint32_t class_count[3])
+{
+    std::vector<uint32_t> order(nruns);
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [runs](uint32_t a, uint32_t b) { return runs[a].size > runs[b].size; });
+    std::vector<int> cls(nruns);
+    uint32_t region_stride = 0;
+    class_count[0] = class_count[1] = class_count[2] = 0;
+    for (uint32_t r = 0; r < nruns; r++) {
+        const cz_fanin_run &f = runs[r];
+        const bool al =
+            ((((uintptr_t)d_in + f.in_off) | f.in_stride | ((uintptr_t)d_out + f.out_off) | f.out_stride) & 15u) == 0;
+        cls[r] = czk_fanin_class(f.out_stride, f.size, f.count, al ? 1 : 0);
+        class_count[cls[r]] += f.count / 64;
+        class_count[CZ_FANOUT_DIRECT] += f.count % 64 ? 1u : 0u;
+        if (cls[r] == CZ_FANOUT_REGION)
+            region_stride = std::max(region_stride, (uint32_t)f.out_stride);
+    }
+    uint32_t at[3] = {0, class_count[0], class_count[0] + class_count[1]};
+    for (uint32_t r : order) {
+        const uint32_t count = runs[r].count;
+        for (uint64_t first = 0; first < count; first += 64)
+            waves[at[first + 64 <= count ? cls[r] : CZ_FANOUT_DIRECT]++] = {r, (uint32_t)first};
+    }
+    return region_stride;
+}
+
 // Split fan-out (cz_plan_fanout_split).  A run's cut points are plan_segments' for one seal descriptor
 // of its length: whole up to 1.5 x seg_blocks blocks, else ceil(nblk / seg_blocks) segments.
 static uint32_t run_blocks(const cz_fanout_run &f) { return (uint32_t)(((uint64_t)f.len + CZ_MESSAGE_OVERHEAD + 63) / 64); }
@@ -633,7 +692,7 @@ int cz_tune(const char *key, int value)
     const struct { const char *name; std::atomic<uint64_t> *knob; uint64_t max; } host_knobs[] = {
         {"nacl_one_max", &g_nacl_one_bytes, czk_nacl_one_limit()},  // bytes; at least one pass of k_nacl_one
         {"fanout_min", &g_fanout_min, INT32_MAX}, {"fanout_short", &g_fanout_short, INT32_MAX},
-        {"fanout_split", &g_fanout_split, INT32_MAX}};
+        {"fanout_split", &g_fanout_split, INT32_MAX}, {"fanin_short", &g_fanin_short, INT32_MAX}};
     for (const auto &h : host_knobs)
         if (key && strcmp(key, h.name) == 0) {
             const int old = (int)h.knob->load(std::memory_order_relaxed);
@@ -877,6 +936,71 @@ int cz_seal_fanout_split(const cz_fanout_run *d_runs, uint32_t nruns, const cz_f
     hipError_t e = czk_seal_fanout_split(d_runs, d_tiles, class_count, d_joins, njoins, d_in, d_subs, d_subkeys, d_out,
                                          d_work, (hipStream_t)stream);
     return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_seal_fanout_split");
+}
+
+// what cz_plan_fanin refuses in a run array, before anything is written
+static int check_fanin_runs(const cz_fanin_run *h_runs, uint32_t nruns)
+{
+    for (uint32_t r = 0; r < nruns; r++) {
+        const cz_fanin_run &f = h_runs[r];
+        const uint64_t nout = f.size >= CZ_MESSAGE_OVERHEAD ? f.size - CZ_MESSAGE_OVERHEAD : 0;
+        if (f.size > 0x7fffffffu)
+            return fail(CZ_EINVAL, "cz_plan_fanin: run %u: body size above 2^31 - 1", r);
+        if (f.count > 1 && (f.in_stride < f.size || f.out_stride < nout))
+            return fail(CZ_EINVAL, "cz_plan_fanin: run %u: stride smaller than the frame", r);
+        if ((uint64_t)f.first_sub + f.count > 0xffffffffull)
+            return fail(CZ_EINVAL, "cz_plan_fanin: run %u: first_sub + count overflows", r);
+        if (f.count == 0)
+            continue;
+        // (bodies and payloads, the whole slots of an owning run: within a 2^47-byte address range)
+        uint64_t in_span = 0, out_span = 0;
+        const bool owns = czk_owns_slots(f.out_stride) != 0;
+        if (__builtin_mul_overflow((uint64_t)f.count - 1, f.in_stride, &in_span) ||
+            __builtin_add_overflow(in_span, (uint64_t)f.size, &in_span) ||
+            __builtin_add_overflow(in_span, f.in_off, &in_span) || in_span > (1ull << 47) ||
+            __builtin_mul_overflow((uint64_t)f.count - (owns ? 0 : 1), f.out_stride, &out_span) ||
+            __builtin_add_overflow(out_span, owns ? 0 : nout, &out_span) ||
+            __builtin_add_overflow(out_span, f.out_off, &out_span) || out_span > (1ull << 47))
+            return fail(CZ_EINVAL, "cz_plan_fanin: run %u: offset + count x stride overflows the address space", r);
+    }
+    return CZ_OK;
+}
+
+int cz_plan_fanin(const cz_fanin_run *h_runs, uint32_t nruns, const void *d_in, const void *d_out,
+                  cz_fanout_wave *h_waves, uint32_t wave_cap, uint32_t *nwaves, uint32_t class_count[3],
+                  uint32_t *region_stride)
+{
+    if ((nruns && (!h_runs || !d_in || !d_out)) || !nwaves || !class_count || !region_stride)
+        return fail(CZ_EINVAL, "cz_plan_fanin: null pointer");
+    if (int rc = check_fanin_runs(h_runs, nruns))
+        return rc;
+    const uint64_t need = fanin_waves(h_runs, nruns);
+    if (need > 0xffffffffull)
+        return fail(CZ_EINVAL, "cz_plan_fanin: more than 2^32 waves");
+    *nwaves = (uint32_t)need;
+    if (need > wave_cap || (need && !h_waves))
+        return fail(CZ_EINVAL, "cz_plan_fanin: capacity too small (need %u waves)", *nwaves);
+    *region_stride = plan_fanin(h_runs, nruns, d_in, d_out, h_waves, class_count);
+    return CZ_OK;
+}
+
+int cz_open_fanin_runs(const cz_fanin_run *d_runs, uint32_t nruns, const cz_fanout_wave *d_waves,
+                       const uint32_t class_count[3], uint32_t region_stride, const void *d_in,
+                       const cz_fanin_sub *d_subs, const void *d_subkeys, void *d_out, uint16_t *d_status,
+                       uint64_t *d_nonces, void *stream)
+{
+    if (!class_count)
+        return fail(CZ_EINVAL, "cz_open_fanin_runs: null pointer");
+    const uint64_t nwaves = (uint64_t)class_count[0] + class_count[1] + class_count[2];
+    if (nruns == 0 || nwaves == 0)
+        return CZ_OK;
+    if (!d_runs || !d_waves || !d_in || !d_subs || !d_subkeys || !d_out || !d_status)
+        return fail(CZ_EINVAL, "cz_open_fanin_runs: null pointer");
+    if (nwaves > 0xffffffffull)
+        return fail(CZ_EINVAL, "cz_open_fanin_runs: more than 2^32 waves");
+    hipError_t e = czk_open_fanin_runs(d_runs, d_waves, class_count, region_stride, d_in, d_subs, d_subkeys, d_out,
+                                       d_status, d_nonces, (hipStream_t)stream);
+    return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_open_fanin_runs");
 }
 
 int cz_seal_uniform_box(uint32_t count, uint32_t len, const void *d_box, uint64_t box_stride, void *d_out,

@@ -32,6 +32,13 @@ uint64_t fanout_waves(const cz_fanout_run *runs, uint32_t nruns);
 uint32_t plan_fanout(const cz_fanout_run *runs, uint32_t nruns, const void *d_in, const void *d_out, cz_fanout_wave *waves,
                      uint32_t class_count[3]);
 
+// The wave table of a fan-in open (cz_plan_fanin) for runs already validated, as plan_fanout: sorted by class,
+// longest body first inside a class; returns the largest region stride.  `waves` must hold fanin_waves(...) records.
+uint32_t fanin_short();  // received runs of a full wave or more with payloads up to this take cz_open_fanin_runs (cz_tune "fanin_short")
+uint64_t fanin_waves(const cz_fanin_run *runs, uint32_t nruns);
+uint32_t plan_fanin(const cz_fanin_run *runs, uint32_t nruns, const void *d_in, const void *d_out, cz_fanout_wave *waves,
+                    uint32_t class_count[3]);
+
 // The tables of a split fan-out (cz_plan_fanout_split) for runs already validated and seg_blocks >= 1:
 // `tiles` / `joins` must hold fanout_split_counts(...).ntiles / .njoins records.
 struct FanoutSplitCounts {

@@ -49,8 +49,8 @@
 #include "../../include/curvezmq_mi355x.h"
 
 // The file compiles as one translation unit (CZ_KPART undefined) or as three that build in parallel
-// (jeromq_amd/build.py: -DCZ_KPART=1 the uniform seal kernels and launchers, 2 the uniform opens,
-// 3 everything else and the run-time knobs); each part instantiates only its own kernels.
+// (jeromq_amd/build.py: -DCZ_KPART=1 the uniform seal kernels and launchers, 2 the uniform opens and
+// the fan-in open, 3 everything else and the run-time knobs); each part instantiates only its own kernels.
 #ifndef CZ_KPART
 #define CZ_KPART 0
 #endif
@@ -3080,6 +3080,106 @@ __global__ __launch_bounds__(BLOCK) CZ_OPEN_CARRY_OCC void k_open_uniform_carry(
     status[i] = (uint16_t)(st | (st == CZ_STATUS_OK ? (fl << 8) : 0u));
 }
 
+// Fan-in open (cz_open_fanin_runs): runs of same-size bodies of many connections in one launch per
+// staging class.  Wave w of this launch's slice of the wave table serves bodies [first, first + 64)
+// of run waves[w].run, one lane per body; the wave index goes through readfirstlane, so the wave and
+// run records are scalar loads and sizes, strides and bases are wave-uniform, as in
+// k_seal_fanout_runs.  Key, floor and check flag are per lane (cz_fanin_sub), so the Salsa rounds
+// are the non-UN0 ones.  A CZ_FANIN_FLOOR_IS_BODY record takes its floor from the wire nonce of the
+// body at that offset of `in`: one 8-byte load when it lies on 8 bytes, byte loads otherwise.
+// The slice's class is a performance choice only: a wave is staged through k_open_uniform's emitter
+// of this instantiation when it is full and ITS run passes that emitter's checks -- bodies, plaintext
+// slots and both strides 16-byte aligned, the stride limits, and for the region emitter 64 slots
+// within the wave's fixed LDS partition (region_part16 x 16 bytes) -- and opens lane-wise otherwise.
+// Staged waves keep k_open_uniform's rule (rejected frames run the loop as dead lanes, so their
+// slots hold zeros); lane-wise lanes write the same zeros themselves, and so does a line-staged lane
+// whose owned slot is longer than its payload's lines: there is no zero-pad launch.
+// No workgroup barrier: the waves of a workgroup may serve different runs or have returned.
+template <int ST, bool PAIR>
+__global__ __launch_bounds__(BLOCK) CZ_OCC CZ_OPEN_UNI_OCC void k_open_fanin_runs(
+    const cz_fanin_run *__restrict__ runs, const cz_fanout_wave *__restrict__ waves, uint32_t nwaves,
+    const uint8_t *__restrict__ in, const cz_fanin_sub *__restrict__ subs, const uint8_t *__restrict__ subkeys,
+    uint8_t *__restrict__ out, uint16_t *__restrict__ status, uint64_t *__restrict__ nonces, uint32_t region_part16)
+{
+    extern __shared__ uint4 smem[];
+    const u32 w = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES + (threadIdx.x >> 6));
+    if (w >= nwaves)
+        return;
+    const cz_fanout_wave wv = waves[w];
+    const cz_fanin_run r = runs[wv.run];
+    if (wv.first >= r.count)
+        return;
+    const u32 lane = threadIdx.x & 63u;
+    const uint8_t *in0 = in + r.in_off;
+    uint8_t *out0 = out + r.out_off;
+    const u32 size = r.size;
+    const u32 nout = size >= 33u ? size - 33u : 0u;
+    const bool full_wave = r.count - wv.first >= 64u;
+    bool staged = ST != ST_DIRECT && full_wave && size >= 33u && r.out_stride != 0 &&
+                  ((((uintptr_t)in0 | r.in_stride | (uintptr_t)out0 | r.out_stride) & 15u) == 0);
+    if constexpr (ST == ST_LINES)
+        staged = staged && r.out_stride % 128 == 0 && nout >= LINES_BYTES_MIN && r.out_stride < LINES_STRIDE_MAX;
+    else if constexpr (ST == ST_REGION)
+        staged = staged && 64 * r.out_stride <= REGION_MAX && ((64 * r.out_stride) >> 4) <= region_part16;
+    if (!staged && lane >= r.count - wv.first)
+        return;
+    const u64 j = (u64)wv.first + lane;
+    const u64 rec = (u64)r.first_sub + j;
+    const cz_fanin_sub sb = subs[rec];
+    u32 key[8];
+    load_key(subkeys + 32ull * sb.key_idx, key);
+    const uint8_t *src = in0 + j * r.in_stride;
+    uint8_t *dst = out0 + j * r.out_stride;
+    long long floor = (long long)sb.floor;
+    if (sb.flags & CZ_FANIN_FLOOR_IS_BODY) {
+        const uint8_t *pb = in + sb.floor + 8;
+        if ((((uintptr_t)pb) & 7u) == 0) {
+            const uint2 pn = *reinterpret_cast<const uint2 *>(pb);
+            floor = (long long)(((u64)bswap32(pn.x) << 32) | (u64)bswap32(pn.y));
+        } else {
+            floor = (long long)read_be64(pb);
+        }
+    }
+    const bool check = (sb.flags & CZ_FANIN_CHECK_NONCE) != 0;
+    u32 fl = 0;
+    u64 nonce = 0;
+    u32 st;
+    if (ST != ST_DIRECT && staged) {
+        if constexpr (ST == ST_LINES) {
+            using EmL = EmitLinesT<CZ_OPEN_STORE_CPOL>;
+            EmL em{smem + (threadIdx.x >> 6) * (LINE_LDS_BYTES / 16), out0 + (u64)wv.first * r.out_stride, dst,
+                   r.out_stride, lane, nout, 0u, false};
+            st = open_frame<MODE_ZMQ, true, EmL, PAIR, false, true, 16>(src, size, key, check, floor, &fl, &nonce, 0, em);
+            // EmitLines ends at the payload's last line; a slot with more lines than that is owned too
+            const u32 lines = (nout + 127u) & ~127u;
+            if (r.out_stride > lines)
+                zero_bytes(dst + lines, (u32)(r.out_stride - lines));
+        } else {
+            EmitRegion em{smem + (threadIdx.x >> 6) * region_part16, out0 + (u64)wv.first * r.out_stride,
+                          (u32)r.out_stride, lane, nout};
+            st = open_frame<MODE_ZMQ, true, EmitRegion, PAIR, false, true, 16>(src, size, key, check, floor, &fl, &nonce,
+                                                                             0, em);
+        }
+    } else {
+        if (aligned16(src, dst)) {
+            EmitDirect<true> em{dst, nout};
+            st = open_frame<MODE_ZMQ, true>(src, size, key, check, floor, &fl, &nonce, 0, em);
+        } else {
+            EmitDirect<false> em{dst, nout};
+            st = open_frame<MODE_ZMQ, false>(src, size, key, check, floor, &fl, &nonce, 0, em);
+        }
+        // the staged waves' contract, as k_open_uniform's lane-wise tail: zeros in the payload of a
+        // frame rejected before decryption, and zeros past the payload in a run that owns its slots
+        if (st != CZ_STATUS_OK && st != CZ_STATUS_CRYPTO)
+            zero_bytes(dst, nout);
+        if (owns_slots(r.out_stride) && r.out_stride > nout)
+            zero_bytes(dst + nout, (u32)(r.out_stride - nout));
+    }
+    status[rec] = (uint16_t)(st | (st == CZ_STATUS_OK ? (fl << 8) : 0u));
+    if (nonces)
+        nonces[rec] = nonce;
+}
+
 #if CZ_KPART_HAS(3)
 // ---- segmented (ragged) batches ------------------------------------------
 // (the mode word's bits, SEGMODE_*: cz_dispatch.h)
@@ -3922,6 +4022,17 @@ Knobs g_knobs;
 #define CZ_INST_OF(l) CZ_INST((l).st, (l).pair, (l).ina)
 #define CZ_LAUNCH(...) hipLaunchKernelGGL(__VA_ARGS__)  // (expands an argument-list macro first)
 
+// k_seal_fanout / k_seal_fanout_runs / k_open_fanin_runs K for the plan l: whole-line input loads except
+// for the region stager
+#define CZ_FAN_CASE(K, ST, PR, l, ...) \
+    case CZ_INST(ST, PR, 16): CZ_LAUNCH((K<ST, PR>), dim3((l).grid), dim3(BLOCK), (l).lds, s, __VA_ARGS__); break;
+#define CZ_FANOUT_SWITCH(K, l, ...)                                                                          \
+    switch (CZ_INST_OF(l)) {                                                                                 \
+        CZ_FAN_CASE(K, ST_LINES, true, l, __VA_ARGS__) CZ_FAN_CASE(K, ST_REGION, false, l, __VA_ARGS__)      \
+        CZ_FAN_CASE(K, ST_DIRECT, true, l, __VA_ARGS__)                                                      \
+    default: return hipErrorInvalidValue;                                                                    \
+    }
+
 extern "C" {
 
 #if CZ_KPART_HAS(1)
@@ -3973,16 +4084,6 @@ hipError_t czk_seal_uniform_box(const void *in, uint64_t in_stride, void *out, u
     return hipGetLastError();
 }
 
-// k_seal_fanout / k_seal_fanout_runs K for the plan l: whole-line input loads except for the region stager
-#define CZ_CASE(K, ST, PR, l, ...) \
-    case CZ_INST(ST, PR, 16): CZ_LAUNCH((K<ST, PR>), dim3((l).grid), dim3(BLOCK), (l).lds, s, __VA_ARGS__); break;
-#define CZ_FANOUT_SWITCH(K, l, ...)                                                                          \
-    switch (CZ_INST_OF(l)) {                                                                                 \
-        CZ_CASE(K, ST_LINES, true, l, __VA_ARGS__) CZ_CASE(K, ST_REGION, false, l, __VA_ARGS__)              \
-        CZ_CASE(K, ST_DIRECT, true, l, __VA_ARGS__)                                                          \
-    default: return hipErrorInvalidValue;                                                                    \
-    }
-
 // PUB fan-out: `count` seals of one payload (k_seal_fanout).  The batch owns whole slots by its
 // stride alone (owns_slots), whatever the base alignments: the staged emitters write the zeros past
 // a body with its lines, the lane-wise path (partial waves, a base or payload off 16-byte
@@ -4023,9 +4124,6 @@ hipError_t czk_seal_fanout_runs(const cz_fanout_run *runs, const cz_fanout_wave 
     }
     return hipGetLastError();
 }
-#undef CZ_FANOUT_SWITCH
-#undef CZ_CASE
-
 #ifdef CZ_DIAG_CLOCK
 // diagnostic builds only: copy the last k_seal_uniform launch's wave stamps (4 x u64 per wave) out
 extern "C" __attribute__((visibility("default"))) int cz_diag_clock_read(uint64_t *host, uint64_t waves)
@@ -4119,6 +4217,31 @@ hipError_t czk_open_uniform(const void *in, uint64_t in_stride, void *out, uint6
             return e;
     }
     return hipGetLastError();
+}
+
+// Fan-in open (k_open_fanin_runs): the wave table holds class_count[CZ_FANOUT_LINES] waves for the line
+// emitter, then class_count[CZ_FANOUT_REGION] for the region emitter, then class_count[CZ_FANOUT_DIRECT]
+// lane-wise ones -- at most three launches whatever the number of runs, and no zero-pad launch.
+hipError_t czk_open_fanin_runs(const cz_fanin_run *runs, const cz_fanout_wave *waves, const uint32_t class_count[3],
+                               uint32_t region_stride, const void *in, const cz_fanin_sub *subs, const void *subkeys,
+                               void *out, uint16_t *status, uint64_t *nonces, hipStream_t s)
+{
+    static_assert(CZ_FANOUT_LINES == 0 && CZ_FANOUT_REGION == 1 && CZ_FANOUT_DIRECT == 2, "classes in table order");
+    const u32 part16 = fanout_region_part16(region_stride);
+    uint32_t w0 = 0;
+    for (int cls = 0; cls < 3; w0 += class_count[cls++]) {
+        if (class_count[cls] == 0)
+            continue;
+        const Launch l = plan_fanin_runs(cls, class_count[cls], part16);
+        CZ_FANOUT_SWITCH(k_open_fanin_runs, l, runs, waves + w0, class_count[cls], (const uint8_t *)in, subs,
+                         (const uint8_t *)subkeys, (uint8_t *)out, status, nonces, part16)
+    }
+    return hipGetLastError();
+}
+
+int czk_fanin_class(uint64_t out_stride, uint32_t size, uint32_t count, int aligned)
+{
+    return plan_fanin_class(out_stride, size, count, aligned != 0);
 }
 
 #ifdef CZ_DIAG_CLOCK

@@ -35,6 +35,13 @@ hipError_t czk_seal_fanout_split(const cz_fanout_run *runs, const cz_fanout_tile
                                  const cz_fanout_join *joins, uint32_t njoins, const void *in,
                                  const cz_fanout_sub *subs, const void *subkeys, void *out, void *work, hipStream_t s);
 
+// fan-in open: runs of same-size bodies of many connections, one lane per body, at most three launches
+hipError_t czk_open_fanin_runs(const cz_fanin_run *runs, const cz_fanout_wave *waves, const uint32_t class_count[3],
+                               uint32_t region_stride, const void *in, const cz_fanin_sub *subs, const void *subkeys,
+                               void *out, uint16_t *status, uint64_t *nonces, hipStream_t s);
+// The staging class cz_plan_fanin gives the full waves of a run.  Host code, no device call.
+int czk_fanin_class(uint64_t out_stride, uint32_t size, uint32_t count, int aligned);
+
 // descriptor and segmented (ragged) batches
 hipError_t czk_seal_desc(const cz_frame_desc *desc, const uint32_t *order, uint32_t count, const void *in, void *out,
                          const void *subkeys, hipStream_t s);

@@ -207,6 +207,12 @@ class CurveBatchEngine:
     def flush_in(self):
         _lib.check(self._L.cz_engine_flush_in(self._h), "cz_engine_flush_in")
 
+    @property
+    def fanin_frames(self):
+        """Frames of the last flush_in that the fan-in open (cz_open_fanin_runs) took out of the segment
+        plan: runs of at least 64 same-size frames with payloads up to cz_tune("fanin_short") bytes."""
+        return int(self._L.cz_engine_fanin_frames(self._h))
+
     def messages_in(self, conn):
         cnt = ctypes.c_uint32()
         _lib.check(self._L.cz_engine_msgs_in(self._h, conn, ctypes.byref(cnt)), "cz_engine_msgs_in")
