@@ -439,6 +439,67 @@ int cz_open_fanin_runs(const cz_fanin_run *d_runs, uint32_t nruns, const cz_fano
                        const cz_fanin_sub *d_subs, const void *d_subkeys, void *d_out,
                        uint16_t *d_status, uint64_t *d_nonces, void *stream);
 
+/* ---- 3g. split fan-in: long received bodies on a connection x segment grid ----------------
+ * Section 3f keeps a body on one lane, so a run takes the time one lane needs for its blocks whatever the
+ * number of connections.  Here the lanes are (run, body, segment), the mirror image of section 3e: a wave
+ * holds 64 bodies of one run on one segment, so size, strides, bases and block range are wave-uniform
+ * and the plan is one 24-byte cz_fanout_tile per WAVE -- no descriptor per frame, no segment record per
+ * (frame, segment).  Runs and per-body records are the cz_fanin_run / cz_fanin_sub arrays of section 3f,
+ * unchanged (CZ_FANIN_CHECK_NONCE, CZ_FANIN_FLOOR_IS_BODY); tiles, joins and classes are the
+ * cz_fanout_tile / cz_fanout_join / CZ_FANOUT_TILE_* of section 3e, with `first` the wave's first body.
+ * Cut points as cz_plan_segments makes them for one open descriptor of the run's size: a body of
+ * nblk = ceil(size / 64) blocks stays whole when nblk <= seg_blocks + seg_blocks / 2, and is
+ * ceil((nblk - 1) / seg_blocks) segments otherwise -- segment 0 covers blocks [0, seg_blocks + 1), segment
+ * s >= 1 starts at block s * seg_blocks + 1, the last one takes the remainder.  seg_blocks == 1 is legal
+ * here: a body of one or two blocks stays whole, a longer one is blocks [0, 2) and then one block per
+ * segment.  The tiles of a split run leave 64-byte Poly1305 partial records in d_work (record
+ * part + lane * nseg for the tile's lane, `part` including the segment's index, so a body's nseg records
+ * are consecutive), and one join lane per (split run, body) combines them, compares with the tag at body
+ * byte 16 and writes the status.
+ * OUTPUT: for every run, byte for byte what cz_open_fanin_runs writes for the same runs and records --
+ * payload bytes, d_status[first_sub + j] (CZ_STATUS_* | flags << 8), d_nonces[first_sub + j] (optional),
+ * zeros over the payload bytes of a frame rejected before decryption and over the plaintext of a frame
+ * whose tag fails, and the ownership rule of cz_open_uniform per run by out_stride alone (an owning
+ * stride gets zeros past each payload and over rejected frames' whole slots; any other stride leaves the
+ * bytes between payloads untouched).  The kernels write their own zeros (no zero-pad launch); nothing
+ * outside the runs' output and record ranges is touched.  The caller keeps the runs' output ranges and
+ * record ranges disjoint, as in section 3f.
+ * A tile's class (CZ_FANOUT_TILE_LINES: a full wave whose body base d_in + in_off and in_stride are
+ * 16-byte aligned, line-staged stores; CZ_FANOUT_TILE_DIRECT: every other tile, lane-wise) only decides
+ * which launch the wave rides in: a wave re-checks its own run, and opens lane-wise when it does not
+ * fit the line emitters or holds a frame rejected before decryption, so a table planned for other
+ * addresses is slower, never wrong.
+ * A caller may build its own tables under the rule of section 3b for open: the tiles of one (run, 64
+ * bodies) cover blocks [0, nblk) contiguously, one or more blocks each, tiles after the first starting at
+ * block 2 or later, in any order in the table, with part = the wave's first record + the segment's index
+ * and the same nseg in each. */
+/* Host-side planner, no device call; d_in and d_out are used as addresses only (alignment class).
+ * seg_blocks == 0: the segment length cz_engine_flush_in picks for a flush of the call's total body
+ * bytes.  Every refusal of cz_plan_fanin applies, checked before anything is written; more than 2^32 - 1
+ * tiles, join waves or partial records: CZ_EINVAL.  *ntiles = sum over runs of segments x
+ * ceil(count / 64), *njoins = sum over split runs of ceil(count / 64), *npart = sum over split runs of
+ * count x segments (d_work must hold 64 bytes each).  A tile_cap / join_cap below that (or a null table)
+ * returns CZ_EINVAL with the three sizes set and nothing else written, as cz_plan_fanout_split.
+ * class_count[c] = tiles of class c; inside a class the tiles with the most output chunks come first.
+ * Replaces StreamEngine.decodeAndPush -> mechanism.decode, once per message and per connection
+ * (StreamEngine.java:1067-1098, CurveClientMechanism.java:166-224, CurveServerMechanism.java:165-225). */
+int cz_plan_fanin_split(const cz_fanin_run *h_runs, uint32_t nruns, const void *d_in, const void *d_out,
+                        uint32_t seg_blocks, cz_fanout_tile *h_tiles, uint32_t tile_cap, uint32_t *ntiles,
+                        uint32_t class_count[2], cz_fanout_join *h_joins, uint32_t join_cap, uint32_t *njoins,
+                        uint32_t *npart);
+/* StreamEngine.decodeAndPush -> mechanism.decode, once per message and per connection
+ * (StreamEngine.java:1067-1098, CurveClientMechanism.java:166-224, CurveServerMechanism.java:165-225):
+ * all of it for R runs, in at most three launches whatever R (tiles of the line class, lane-wise tiles,
+ * join).  d_runs / d_tiles / d_joins: device copies of the run array and of the planner's tables;
+ * class_count as the planner returned it.  Asynchronous on `stream`; allocates nothing; never
+ * synchronises; can be captured into a graph.  nruns == 0 or no tiles: CZ_OK, nothing launched.  Null
+ * pointers (d_joins / d_work only when njoins != 0; d_nonces is optional): CZ_EINVAL, checked before the
+ * device is touched.  No device: CZ_EHIP; there is no CPU fallback. */
+int cz_open_fanin_split(const cz_fanin_run *d_runs, uint32_t nruns, const cz_fanout_tile *d_tiles,
+                        const uint32_t class_count[2], const cz_fanout_join *d_joins, uint32_t njoins,
+                        const void *d_in, const cz_fanin_sub *d_subs, const void *d_subkeys, void *d_out,
+                        void *d_work, uint16_t *d_status, uint64_t *d_nonces, void *stream);
+
 /* Synthetic data: fill d_buf with the counter-based SplitMix64 byte stream (seed). */
 int cz_fill(void *d_buf, uint64_t nbytes, uint64_t seed, void *stream);
 /* Measurement: device-to-device copy of nbytes (a multiple of 16) with 16-byte loads and stores,
@@ -620,11 +681,15 @@ int cz_engine_recv_commit(cz_engine *e, int conn, uint64_t n);
  * group (connection by connection, each connection's frames in order) a run of at least 64 consecutive
  * frames of one body size whose payload is at most cz_tune("fanin_short") bytes leaves the segment plan,
  * and all such runs of the group are one cz_open_fanin_runs call (section 3f); a run may span
- * connection edges.  Delivered messages, cnPeerNonce, errors and events are those of the unrouted
- * flush. */
+ * connection edges.  Every other such run whose payload is at least cz_tune("fanin_split") bytes leaves
+ * the segment plan too, for the group's one cz_open_fanin_split call (section 3g) at the flush's own
+ * segment length; a run cut by a group edge is two runs.  Delivered messages, cnPeerNonce, errors and
+ * events are those of the unrouted flush. */
 int cz_engine_flush_in(cz_engine *e);
 /* frames of the last cz_engine_flush_in that its cz_open_fanin_runs calls opened (0: nothing was routed) */
 uint64_t cz_engine_fanin_frames(const cz_engine *e);
+/* ... and that its cz_open_fanin_split calls opened */
+uint64_t cz_engine_fanin_split_frames(const cz_engine *e);
 /* decoded messages of the last cz_engine_flush_in (pinned memory, valid until the next one) */
 int cz_engine_msgs_in(cz_engine *e, int conn, uint32_t *count);
 int cz_engine_msg_in(cz_engine *e, int conn, uint32_t i, const uint8_t **payload, uint32_t *len, int *msg_flags);
@@ -899,7 +964,17 @@ int cz_device_ok(void);
  *              R x N >= 1024 (100 B: 0.0104 against 0.0122 ms for 16 runs of 1024 bodies; 256 B: 0.0142 against
  *              0.0151 ms; 1024 B: 0.0394 against 0.0304 ms, so not 1024) and the routed flush of 1024 connections x
  *              16 frames is not slower than the unrouted one (100 B: 1.447 against 1.447 ms; 256 B: 1.567 against
- *              1.554 ms, so not 256: such a flush is host- and copy-bound); profiles/fanin/fanin.json */
+ *              1.554 ms, so not 256: such a flush is host- and copy-bound); profiles/fanin/fanin.json
+ *   "fanin_split": every other such run of at least 64 received frames whose payload is at least this many bytes leaves
+ *              the segment plan for the flush group's one cz_open_fanin_split call (section 3g), cut at the flush's
+ *              own segment length; fanin_short keeps precedence; 0 = rule off.  Default 0: the rule that set
+ *              fanout_split asks the split call to be not slower than cz_open_segments at every R x N >= 1024 at every
+ *              measured length from the default up, and the routed flush_in of 1024 connections x 16 and x 256 frames
+ *              to be not slower than the unrouted one.  The split call is ahead at 19 of 20 shapes (4 KiB: 0.0585
+ *              against 0.0597 ms for 16 runs of 1024 bodies; 16 KiB: 0.1850 against 0.1865 ms) and the routed flush at
+ *              all 8 (1 KiB x 16: 2.03 against 3.39 ms; 64 KiB x 256: 368.8 against 370.3 ms), but 64 KiB loses one
+ *              shape (16 runs of 1024 bodies: 0.6197 against 0.6033 ms), so no length qualifies.  A caller whose runs
+ *              stay below 64 KiB can set 1024; profiles/fanin/fanin_split.json */
 int cz_tune(const char *key, int value);
 
 #ifdef __cplusplus

@@ -164,6 +164,10 @@ SIGNATURES = {
     "cz_plan_fanin": (_I, [_VP, _U32, _VP, _VP, _VP, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32),
                            ctypes.POINTER(_U32)]),
     "cz_open_fanin_runs": (_I, [_VP, _U32, _VP, ctypes.POINTER(_U32), _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "cz_plan_fanin_split": (_I, [_VP, _U32, _VP, _VP, _U32, _VP, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32), _VP,
+                                 _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    "cz_open_fanin_split": (_I, [_VP, _U32, _VP, ctypes.POINTER(_U32), _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                 _VP]),
     "cz_plan_order": (_I, [_VP, _U32, _VP]),
     "cz_plan_segments": (_I, [_VP, _U32, _I, _U32, _VP, _U32, ctypes.POINTER(_U32), _VP, _U32,
                               ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
@@ -213,6 +217,7 @@ SIGNATURES = {
     "cz_engine_nonce": (_U64, [_VP, _I]),
     "cz_engine_peer_nonce": (_U64, [_VP, _I]),
     "cz_engine_fanin_frames": (_U64, [_VP]),
+    "cz_engine_fanin_split_frames": (_U64, [_VP]),
     "cz_scalarmult": (_I, [_VP, _VP, _VP]),
     "cz_box_keypair": (_I, [_VP, _VP]),
     "cz_box_beforenm": (_I, [_VP, _VP, _VP]),

@@ -300,6 +300,68 @@ def seal_fanout_split(plan, inp, subs, subkeys_t, out, work=None, stream=None):
     return work
 
 
+class FaninSplitPlan(FanoutSplitPlan):
+    """Host plan of a split fan-in open (cz_plan_fanin_split): the runs (FANIN_RUN_DTYPE) and, as
+    FanoutSplitPlan, `tiles` (one per wave of 64 bodies and per segment, sorted by class), `class_count`,
+    `joins` and `npart`.  `to(device)` uploads the three tables.  A caller may replace `tiles`, `joins`,
+    `class_count` and `npart` with tables of its own before `to`."""
+
+    def to(self, device):
+        import torch
+
+        def up(a, dt):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=dt).view(np.uint8).copy()).to(device)
+        self.d_runs = up(self.runs, FANIN_RUN_DTYPE)
+        self.d_tiles = up(self.tiles, FANOUT_TILE_DTYPE)
+        self.d_joins = up(self.joins, FANOUT_JOIN_DTYPE)
+        return self
+
+
+def plan_fanin_split(runs_np, inp, out, seg_blocks=0):
+    """Plan the split fan-in open of `runs_np` (FANIN_RUN_DTYPE) reading `inp` and writing `out`: device
+    tensors (or plain addresses), used as addresses only (`inp` for the tiles' class).  seg_blocks 0: the
+    length flush_in picks for a flush of the runs' total body bytes.  Returns a FaninSplitPlan."""
+    r = np.ascontiguousarray(runs_np, dtype=FANIN_RUN_DTYPE)
+    a_in, a_out = (t if isinstance(t, int) else t.data_ptr() for t in (inp, out))
+    nt, nj, npart, cc = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32(), (ctypes.c_uint32 * 2)()
+    L = _lib.lib()
+    L.cz_plan_fanin_split(r.ctypes.data, len(r), a_in, a_out, seg_blocks, None, 0, ctypes.byref(nt), cc, None, 0,
+                          ctypes.byref(nj), ctypes.byref(npart))
+    tiles = np.zeros(max(nt.value, 1), dtype=FANOUT_TILE_DTYPE)
+    joins = np.zeros(max(nj.value, 1), dtype=FANOUT_JOIN_DTYPE)
+    _lib.check(L.cz_plan_fanin_split(r.ctypes.data, len(r), a_in, a_out, seg_blocks, tiles.ctypes.data, len(tiles),
+                                     ctypes.byref(nt), cc, joins.ctypes.data, len(joins), ctypes.byref(nj),
+                                     ctypes.byref(npart)), "cz_plan_fanin_split")
+    return FaninSplitPlan(r, tiles[:nt.value], cc, joins[:nj.value], npart.value)
+
+
+def open_fanin_split(plan, inp, subs, subkeys_t, out, status, nonces=None, work=None, stream=None, subs_np=None):
+    """Split fan-in open: every run of `plan` (plan_fanin_split(...).to(device)) opened on a connection x
+    segment grid in at most three launches; every run gets what open_fanin_runs writes for it.  Records,
+    statuses and nonces as open_fanin_runs.  `work`: 64 * plan.npart bytes of device scratch, allocated
+    when not given.  Bounds are checked as open_fanin_runs checks them."""
+    import torch
+    _need_cuda_u8(inp, "in")
+    _need_cuda_u8(out, "out")
+    _need_cuda_u8(subkeys_t, "subkeys")
+    if subs is None or not subs.is_cuda or status is None or not status.is_cuda:
+        raise ValueError("subs and status must be CUDA (HIP) tensors")
+    if plan.nruns and plan.d_runs is None:
+        raise ValueError("plan not uploaded: plan.to(device)")
+    _check_fanin_bounds(plan.runs, inp, out, subs_np, subs.numel() * subs.element_size() // FANIN_SUB_DTYPE.itemsize,
+                        status, nonces)
+    if work is None:
+        work = torch.empty(max(plan.npart, 1) * 64, dtype=torch.uint8, device=out.device)
+    elif work.numel() * work.element_size() < 64 * plan.npart:
+        raise ValueError("work smaller than 64 * plan.npart bytes")
+    cc = (ctypes.c_uint32 * 2)(*plan.class_count)
+    _lib.check(_lib.lib().cz_open_fanin_split(_ptr(plan.d_runs), plan.nruns, _ptr(plan.d_tiles), cc,
+                                              _ptr(plan.d_joins), len(plan.joins), _ptr(inp), _ptr(subs),
+                                              _ptr(subkeys_t), _ptr(out), _ptr(work), _ptr(status), _ptr(nonces),
+                                              _stream(stream)), "cz_open_fanin_split")
+    return work
+
+
 def seal_uniform_box(box, box_stride, out, out_stride, count, length, subkey, counter0, stream=None):
     """Uniform seal from the reference's box layout: slot i of `box` holds 0^32 || flags ||
     payload (length = payload bytes), as CurveClientMechanism.encode hands it to Curve.afternm."""

@@ -82,7 +82,7 @@ struct Knobs {
 };
 
 // ---- what a launcher launches -----------------------------------------------
-enum Family { K_SEAL_UNIFORM, K_SEAL_UNIFORM_INA, K_SEAL_FANOUT, K_OPEN_UNIFORM, K_OPEN_UNIFORM_CARRY, K_SEAL_FANOUT_TILES, K_OPEN_FANIN };
+enum Family { K_SEAL_UNIFORM, K_SEAL_UNIFORM_INA, K_SEAL_FANOUT, K_OPEN_UNIFORM, K_OPEN_UNIFORM_CARRY, K_SEAL_FANOUT_TILES, K_OPEN_FANIN, K_OPEN_FANIN_TILES };
 constexpr int64_t PAD_NONE = -1;
 
 struct Launch {
@@ -255,6 +255,15 @@ inline Launch plan_fanout_tiles(int cls, uint32_t ntiles)
 {
     const int st = cls == CZ_FANOUT_TILE_LINES ? ST_LINES : ST_DIRECT;
     return Launch{K_SEAL_FANOUT_TILES, st, true, 16, MODE_ZMQ, (ntiles + WAVES - 1) / WAVES,
+                  st == ST_LINES ? WAVES * SHIFT_LDS_BYTES : 0u, PAD_NONE};
+}
+
+// czk_open_fanin_split: one class's slice of the tile table, one wave per tile; the line class stages
+// through k_open_segments' rows (EmitSegLines / EmitShiftLines), the lane-wise class needs no LDS
+inline Launch plan_fanin_tiles(int cls, uint32_t ntiles)
+{
+    const int st = cls == CZ_FANOUT_TILE_LINES ? ST_LINES : ST_DIRECT;
+    return Launch{K_OPEN_FANIN_TILES, st, true, 16, MODE_ZMQ, (ntiles + WAVES - 1) / WAVES,
                   st == ST_LINES ? WAVES * SHIFT_LDS_BYTES : 0u, PAD_NONE};
 }
 

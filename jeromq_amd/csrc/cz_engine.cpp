@@ -43,17 +43,8 @@ using namespace czi;
 namespace {
 
 constexpr uint64_t SLOT_ALIGN = 128;  // body / payload slots: line-staged stores, whole-line loads
-constexpr uint32_t SEG_BLOCKS = 128;  // as jeromq_amd.batch.SEG_BLOCKS
 
-// Segment length for a received flush of `blocks` 64-byte blocks in all (frame sizes are known
-// only after the parse): SEG_BLOCKS once there are 64K lanes' worth, shorter below that (down to
-// 4) so that a small flush spreads each frame over many lanes instead of walking it on one (a
-// 4 KiB frame alone: 65 blocks on one lane, ~150 us).  flush_out knows its lengths up front and
-// uses batch_seg_blocks.
-uint32_t flush_seg_blocks(uint64_t blocks)
-{
-    return (uint32_t)std::min<uint64_t>(SEG_BLOCKS, std::max<uint64_t>(4, (blocks + 65535) / 65536));
-}
+// (flush_in's segment length, flush_seg_blocks: cz_internal.h, shared with cz_plan_fanin_split)
 
 uint64_t round_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 
@@ -267,6 +258,7 @@ struct cz_engine {
         d_ftiles, d_fjoins, d_fwork;  // split fan-out: tile and join tables, partial records
     uint32_t pub_seq = 0;  // id of the last cz_engine_publish call (OutMsg::pub)
     uint64_t fanin_frames = 0;  // frames of the last flush_in that its cz_open_fanin_runs calls opened
+    uint64_t fanin_split_frames = 0;  // ... and that its cz_open_fanin_split calls opened
     HostBuf h_status, h_nonces;
     HostBuf h_meta;  // pinned staging of descriptors / items / segment lists (async H2D)
     RxPool rxpool;   // every connection's receive buffer
@@ -630,6 +622,7 @@ struct cz_engine {
         PhaseTimer pt("flush_in");
         in_msgs.clear();
         fanin_frames = 0;
+        fanin_split_frames = 0;
         for (Conn &c : conns)
             c.in_msgs.clear();
         // 0. the live connections, in groups of ~equal received bytes
@@ -758,13 +751,20 @@ struct cz_engine {
             std::vector<std::pair<uint32_t, uint32_t>> runs;  // (first, count)
             std::vector<uint8_t> routed;
             uint64_t nfwave = 0, nrouted = 0;
+            // split fan-in: the other such runs whose payload is at least cz_tune("fanin_split") bytes are
+            // the group's cz_open_fanin_split call at the flush's own segment length: they extend the run
+            // table, and their tiles, joins and partial records are counted here, before any descriptor
+            // exists (fanin_split_counts, as plan_counts for the segment plan)
+            std::vector<std::pair<uint32_t, uint32_t>> sruns;  // (first, count)
+            uint64_t stiles = 0, sjoins = 0, spart = 0, nsrouted = 0;
             // its fan-in block in the metadata staging and in d_subs: records by group-relative frame index,
-            // then the run table, then the wave table -- one upload
+            // then the run table (fan-in runs, then split runs), the wave table, the tile table and the
+            // join table -- one upload
             uint64_t foff = 0, fbytes = 0;
-            uint32_t fclass[3] = {0, 0, 0}, fregion = 0;
+            uint32_t fclass[3] = {0, 0, 0}, fregion = 0, sclass[2] = {0, 0};
         };
         std::vector<GroupWork> gw(groups.size());
-        const uint32_t fin_short = fanin_short();
+        const uint32_t fin_short = fanin_short(), fin_split = fanin_split();
         auto parse = [&](size_t gi) {
             GroupWork &w = gw[gi];
             const Group &g = groups[gi];
@@ -795,21 +795,37 @@ struct cz_engine {
                 p.perr = prc == CZ_OK ? 0 : prc;
             }
             const uint32_t gn = (uint32_t)w.frames.size();
-            for (uint32_t i = 0; fin_short && i < gn;) {
+            for (uint32_t i = 0; (fin_short || fin_split) && i < gn;) {
                 uint32_t j = i + 1;
                 while (j < gn && w.frames[j].size == w.frames[i].size)
                     j++;
-                if (j - i >= 64u && w.frames[i].size >= CZ_MESSAGE_OVERHEAD &&
-                    w.frames[i].size - CZ_MESSAGE_OVERHEAD <= fin_short) {
+                const bool full = j - i >= 64u && w.frames[i].size >= CZ_MESSAGE_OVERHEAD;
+                const uint32_t plen = full ? w.frames[i].size - CZ_MESSAGE_OVERHEAD : 0u;
+                const bool by_short = full && fin_short && plen <= fin_short;  // (keeps precedence)
+                const bool by_split = full && !by_short && fin_split && plen >= fin_split;
+                if (by_short || by_split) {
                     if (w.routed.empty())
                         w.routed.assign(gn, 0);
                     std::fill(w.routed.begin() + i, w.routed.begin() + j, (uint8_t)1);
+                }
+                if (by_short) {
                     w.runs.push_back({i, j - i});
                     w.nfwave += ((uint64_t)(j - i) + 63) / 64;
                     w.nrouted += j - i;
                 }
+                if (by_split) {
+                    const cz_fanin_run one{0, 0, 0, 0, w.frames[i].size, 0u, j - i, 0u};
+                    const FanoutSplitCounts sc = fanin_split_counts(&one, 1, seg);
+                    w.sruns.push_back({i, j - i});
+                    w.stiles += sc.ntiles;
+                    w.sjoins += sc.njoins;
+                    w.spart += sc.npart;
+                    w.nsrouted += j - i;
+                }
                 i = j;
             }
+            if (w.stiles > 0xffffffffull || w.spart > 0xffffffffull)
+                w.bad_plan = true;
             for (uint32_t i = 0; i < gn; i++) {
                 const cz_v2_frame &f = w.frames[i];
                 const uint64_t plen = f.size > CZ_MESSAGE_OVERHEAD ? f.size - CZ_MESSAGE_OVERHEAD : 0;
@@ -837,11 +853,13 @@ struct cz_engine {
             Group &g = groups[gi];
             GroupWork &w = gw[gi];
             w.foff = nfan;
-            if (!w.runs.empty())
-                w.fbytes = w.frames.size() * sizeof(cz_fanin_sub) + w.runs.size() * sizeof(cz_fanin_run) +
-                           w.nfwave * sizeof(cz_fanout_wave);
+            if (!w.runs.empty() || !w.sruns.empty())
+                w.fbytes = w.frames.size() * sizeof(cz_fanin_sub) +
+                           (w.runs.size() + w.sruns.size()) * sizeof(cz_fanin_run) + w.nfwave * sizeof(cz_fanout_wave) +
+                           w.stiles * sizeof(cz_fanout_tile) + w.sjoins * sizeof(cz_fanout_join);
             nfan += w.fbytes;
             fanin_frames += w.nrouted;
+            fanin_split_frames += w.nsrouted;
             g.fa = n;
             for (size_t q = g.pa; q < g.pb; q++)
                 parsed[q].first += n;
@@ -856,7 +874,7 @@ struct cz_engine {
             pslot += w.pslot;
             nseg += w.nseg;
             ncomb += w.ncomb;
-            npart += w.npart;
+            npart += w.npart + w.spart;  // (the split runs' partial records behind the segment plan's)
             g.pl1 = pslot;
         }
         const uint64_t m_items = 0, m_desc = (uint64_t)n * sizeof(cz_v2_item),
@@ -912,7 +930,9 @@ struct cz_engine {
                 }
             }
             const uint32_t gn = g.fb - g.fa;
-            if (w.runs.empty()) {
+            if (w.bad_plan)
+                return;
+            if (w.runs.empty() && w.sruns.empty()) {
                 plan_segments(desc, gn, 1, seg, w.sg.seg, w.sg.comb, w.sg.npart);
             } else {
                 // Fan-in records of the routed frames, at the frame's index in the group (where its
@@ -922,7 +942,10 @@ struct cz_engine {
                 // segment plan resolve through them, and the delivery step reads them.
                 cz_fanin_sub *h_isubs = (cz_fanin_sub *)(h_fanin + w.foff);
                 cz_fanin_run *hr = (cz_fanin_run *)(h_isubs + gn);
-                cz_fanout_wave *hw = (cz_fanout_wave *)(hr + w.runs.size());
+                cz_fanin_run *hs = hr + w.runs.size();  // the split runs
+                cz_fanout_wave *hw = (cz_fanout_wave *)(hs + w.sruns.size());
+                cz_fanout_tile *ht = (cz_fanout_tile *)(hw + w.nfwave);
+                cz_fanout_join *hj = (cz_fanout_join *)(ht + w.stiles);
                 for (size_t q = g.pa; q < g.pb; q++) {
                     const Parsed &p = parsed[q];
                     const Conn &c = conns[p.conn];
@@ -935,19 +958,23 @@ struct cz_engine {
                                               : cz_fanin_sub{c.peer_nonce, c.rx_key, CZ_FANIN_CHECK_NONCE};
                     }
                 }
-                for (size_t r = 0; r < w.runs.size(); r++) {
-                    const uint32_t first = w.runs[r].first, size = desc[first].len;
+                for (size_t r = 0; r < w.runs.size() + w.sruns.size(); r++) {
+                    const auto &run = r < w.runs.size() ? w.runs[r] : w.sruns[r - w.runs.size()];
+                    const uint32_t first = run.first, size = desc[first].len;
                     hr[r] = {desc[first].in_off, round_up(size, SLOT_ALIGN), desc[first].out_off,
                              round_up(std::max<uint64_t>(size - CZ_MESSAGE_OVERHEAD, 1), SLOT_ALIGN), size, first,
-                             w.runs[r].second, 0u};
+                             run.second, 0u};
                 }
-                w.fregion = plan_fanin(hr, (uint32_t)w.runs.size(), d_in.ptr, d_plain.ptr, hw, w.fclass);
+                if (!w.runs.empty())
+                    w.fregion = plan_fanin(hr, (uint32_t)w.runs.size(), d_in.ptr, d_plain.ptr, hw, w.fclass);
+                if (!w.sruns.empty())
+                    plan_fanin_split(hs, (uint32_t)w.sruns.size(), d_in.ptr, seg, ht, w.sclass, hj);
                 // the segment plan of the frames that stay: planned over a packed copy of their
                 // descriptors, then named by their index in the whole array
                 std::vector<cz_frame_desc> rest;
                 std::vector<uint32_t> index;
-                rest.reserve(gn - w.nrouted);
-                index.reserve(gn - w.nrouted);
+                rest.reserve(gn - w.nrouted - w.nsrouted);
+                index.reserve(gn - w.nrouted - w.nsrouted);
                 for (uint32_t i = 0; i < gn; i++)
                     if (!w.routed[i]) {
                         rest.push_back(desc[i]);
@@ -977,12 +1004,17 @@ struct cz_engine {
             cz_frame_desc *dd = (cz_frame_desc *)d_desc.ptr + g.fa;
             cz_segment *dsg = (cz_segment *)d_seg.ptr + w.soff;
             cz_combine *dcb = (cz_combine *)d_comb.ptr + w.coff;
-            const uint32_t nr = (uint32_t)w.runs.size();
-            // the group's fan-in block on the device: records, runs, waves, laid out as in the staging
+            const uint32_t nr = (uint32_t)w.runs.size(), nsr = (uint32_t)w.sruns.size();
+            // the group's fan-in block on the device: records, runs, waves, tiles, joins, laid out as in the staging
             const cz_fanin_sub *dis = (const cz_fanin_sub *)((const uint8_t *)d_subs.ptr + w.foff);
             const cz_fanin_run *dir = (const cz_fanin_run *)(dis + gn);
-            const cz_fanout_wave *diw = (const cz_fanout_wave *)(dir + nr);
-            const uint64_t sub_a = nr ? (uint64_t)w.runs.front().first * sizeof(cz_fanin_sub) : 0u;  // first record used
+            const cz_fanin_run *dsr = dir + nr;
+            const cz_fanout_wave *diw = (const cz_fanout_wave *)(dsr + nsr);
+            const cz_fanout_tile *dst = (const cz_fanout_tile *)(diw + w.nfwave);
+            const cz_fanout_join *dsj = (const cz_fanout_join *)(dst + w.stiles);
+            // first record used
+            const uint64_t sub_a = (uint64_t)std::min(nr ? w.runs.front().first : UINT32_MAX,
+                                                      nsr ? w.sruns.front().first : UINT32_MAX) * sizeof(cz_fanin_sub);
             hipError_t r;
             // (a) metadata stream: the group's descriptors / items / segment lists
             if ((r = hipMemcpyAsync((cz_v2_item *)d_items.ptr + g.fa, h_items + g.fa, (uint64_t)gn * sizeof(cz_v2_item),
@@ -994,7 +1026,7 @@ struct cz_engine {
                 (w.sg.ncomb && (r = hipMemcpyAsync(dcb, h_comb + w.coff, (uint64_t)w.sg.ncomb * sizeof(cz_combine),
                                                    hipMemcpyHostToDevice, qm)) != hipSuccess) ||
                 // (one copy for the group's fan-in block, from the first routed frame's record on)
-                (nr && (r = hipMemcpyAsync((uint8_t *)d_subs.ptr + w.foff + sub_a, h_fanin + w.foff + sub_a,
+                ((nr || nsr) && (r = hipMemcpyAsync((uint8_t *)d_subs.ptr + w.foff + sub_a, h_fanin + w.foff + sub_a,
                                            w.fbytes - sub_a, hipMemcpyHostToDevice, qm)) != hipSuccess) ||
                 (qm != qk && (r = hipEventRecord(evm[gi], qm)) != hipSuccess))
                 return r;
@@ -1008,6 +1040,11 @@ struct cz_engine {
                 (nr && (r = czk_open_fanin_runs(dir, diw, w.fclass, w.fregion, d_in.ptr, dis, subkeys.ptr, d_plain.ptr,
                                                 (uint16_t *)d_status.ptr + g.fa, (uint64_t *)d_nonces.ptr + g.fa,
                                                 qk)) != hipSuccess) ||
+                // ... its split runs on the connection x segment grid, at the flush's own segment length
+                (nsr && (r = czk_open_fanin_split(dsr, dst, w.sclass, dsj, (uint32_t)w.sjoins, d_in.ptr, dis, subkeys.ptr,
+                                                  d_plain.ptr, (uint8_t *)d_work.ptr + 64 * (w.woff + w.npart),
+                                                  (uint16_t *)d_status.ptr + g.fa, (uint64_t *)d_nonces.ptr + g.fa,
+                                                  qk)) != hipSuccess) ||
                 (w.sg.nseg &&
                  (r = czk_open_segments(dd, dsg, w.sg.nseg, dcb, w.sg.ncomb, d_in.ptr, d_plain.ptr, subkeys.ptr,
                                         (uint8_t *)d_work.ptr + 64 * w.woff, (uint16_t *)d_status.ptr + g.fa,
@@ -1642,5 +1679,6 @@ uint64_t cz_engine_peer_nonce(cz_engine *e, int conn)
 }
 
 uint64_t cz_engine_fanin_frames(const cz_engine *e) { return e ? e->fanin_frames : 0; }
+uint64_t cz_engine_fanin_split_frames(const cz_engine *e) { return e ? e->fanin_split_frames : 0; }
 
 }  // extern "C"

@@ -302,6 +302,28 @@ static std::atomic<uint64_t> g_fanin_short{100};
 
 uint32_t fanin_short() { return (uint32_t)g_fanin_short.load(std::memory_order_relaxed); }
 
+// cz_engine_flush_in: a run of at least 64 consecutive received frames (one full wave) of one body size
+// that fanin_short does not take and whose payload is at least this many bytes leaves the segment plan
+// for the flush group's one cz_open_fanin_split call, cut at the flush's own segment length; 0 = rule
+// off (cz_tune "fanin_split").
+// The rule for the default, set before any run, is fanout_split's: the smallest measured length L (of
+// 1024, 4096, 16 384, 65 536) such that at every measured length >= L the split call (e) is not slower
+// than cz_open_segments at the same segment length (b) in the median at every measured R x N >= 1024,
+// and the flush routed by it is not slower than the unrouted flush at both engine shapes
+// (tools/fanin_bench.py --split, profiles/fanin/fanin_split.json, medians of 7, legs interleaved).
+// Default 0 by that rule: no length qualifies, because the largest one loses one device shape.
+//   len     (e) / (b) ms at R x N = 1024 (1 x 1024), 16 384, 262 144    flush_in ms, routed / unrouted, x 16 and x 256 frames
+//   1024    0.0210 / 0.0227   0.0289 / 0.0297   0.1518 / 0.1543         2.03 / 3.39     8.81 / 8.88
+//   4096    0.0278 / 0.0298   0.0585 / 0.0597   0.5648 / 0.5792         3.66 / 3.72     24.95 / 25.13
+//   16384   0.0543 / 0.0551   0.1850 / 0.1865   2.2288 / 2.2556         8.90 / 8.98     92.49 / 92.73
+//   65536   0.0923 / 0.0945   0.6197 / 0.6033   8.7172 / 8.7759         28.21 / 28.46   368.8 / 370.3
+// (e) is ahead at 19 of 20 shapes (0.4-11%) and the routed flush at all 8, but 64 KiB x 16 384 lanes is 2.7% behind
+// (0.6197 against 0.6033 ms, rounds 0.599-0.649 against 0.594-0.609), and the rule asks every length from L up to
+// pass.  A caller whose received runs stay below 64 KiB can set the knob to 1024.
+static std::atomic<uint64_t> g_fanin_split{0};
+
+uint32_t fanin_split() { return (uint32_t)g_fanin_split.load(std::memory_order_relaxed); }
+
 // NaCl box/open of one message on the device.  A MESSAGE is the NaCl box of
 // 0^32 || flags || payload, so m[32] rides as the flags byte and m[33:] as the payload; for open
 // the 16 bytes ahead of the tag are rebuilt as "\x07MESSAGE" || n[16:24] and the nonce check is off.
@@ -656,6 +678,86 @@ void plan_fanout_split(const cz_fanout_run *runs, uint32_t nruns, const void *d_
     }
 }
 
+// Split fan-in open (cz_plan_fanin_split).  A run's cut points are plan_segments' for one open descriptor
+// of its size: whole up to 1.5 x seg_blocks blocks, else ceil((nblk - 1) / seg_blocks) segments, segment
+// s >= 1 starting at block s * seg_blocks + 1.  seg_blocks 1 (which cz_plan_segments refuses): a body
+// of two blocks is one segment by that count and stays whole; a longer one is segment 0 = blocks
+// [0, 2), then one block each.
+static uint32_t fanin_blocks(const cz_fanin_run &f) { return f.size ? (uint32_t)(((uint64_t)f.size + 63) / 64) : 1u; }
+static uint32_t fanin_segments(const cz_fanin_run &f, uint32_t seg_blocks)
+{
+    const uint32_t nblk = fanin_blocks(f);
+    return nblk <= seg_blocks + seg_blocks / 2 ? 1u : (nblk - 1 + seg_blocks - 1) / seg_blocks;
+}
+
+uint32_t fanin_split_seg_blocks(const cz_fanin_run *runs, uint32_t nruns)
+{
+    uint64_t bytes = 0;
+    for (uint32_t r = 0; r < nruns; r++)
+        bytes += (uint64_t)runs[r].count * runs[r].size;
+    return flush_seg_blocks(bytes / 64);
+}
+
+FanoutSplitCounts fanin_split_counts(const cz_fanin_run *runs, uint32_t nruns, uint32_t seg_blocks)
+{
+    FanoutSplitCounts c{0, 0, 0};
+    for (uint32_t r = 0; r < nruns; r++) {
+        const uint64_t waves = ((uint64_t)runs[r].count + 63) / 64, ns = fanin_segments(runs[r], seg_blocks);
+        c.ntiles += waves * ns;
+        if (ns > 1) {
+            c.njoins += waves;
+            c.npart += (uint64_t)runs[r].count * ns;
+        }
+    }
+    return c;
+}
+
+// Tiles in run, segment, wave order, then a stable sort by class and output chunk count (most chunks
+// first, the kernel's loop count as plan_segments keys it), so the waves of one (run, segment) stay
+// neighbours and a long tile does not start last.  A full wave of a run whose body base and in_stride
+// are on 16 bytes is of the line class.
+void plan_fanin_split(const cz_fanin_run *runs, uint32_t nruns, const void *d_in, uint32_t seg_blocks,
+                      cz_fanout_tile *tiles, uint32_t class_count[2], cz_fanout_join *joins)
+{
+    std::vector<cz_fanout_tile> all;
+    std::vector<uint8_t> cls;
+    std::vector<uint32_t> chunks;
+    uint64_t part = 0;
+    uint32_t nj = 0;
+    for (uint32_t r = 0; r < nruns; r++) {
+        const cz_fanin_run &f = runs[r];
+        const uint32_t nblk = fanin_blocks(f), ns = fanin_segments(f, seg_blocks);
+        const bool in_al = ((((uintptr_t)d_in + f.in_off) | f.in_stride) & 15u) == 0;
+        for (uint32_t s = 0; s < ns; s++) {
+            const uint32_t b0 = s ? s * seg_blocks + 1 : 0u, b1 = s + 1 < ns ? (s + 1) * seg_blocks + 1 : nblk;
+            uint32_t nch = 0;
+            if (f.size >= CZ_MESSAGE_OVERHEAD)
+                nch = (b1 == nblk ? (f.size - CZ_MESSAGE_OVERHEAD + 63) / 64 : b1 - 1) - (b0 ? b0 - 1 : 0u);
+            for (uint64_t first = 0; first < f.count; first += 64) {
+                const uint32_t p = ns > 1 ? (uint32_t)(part + first * ns + s) : 0xffffffffu;
+                all.push_back({r, (uint32_t)first, b0, b1 - b0, p, ns});
+                cls.push_back(in_al && first + 64 <= f.count ? CZ_FANOUT_TILE_LINES : CZ_FANOUT_TILE_DIRECT);
+                chunks.push_back(nch);
+            }
+        }
+        if (ns > 1) {
+            for (uint64_t first = 0; first < f.count; first += 64)
+                joins[nj++] = {r, (uint32_t)first, (uint32_t)(part + first * ns), ns};
+            part += (uint64_t)f.count * ns;
+        }
+    }
+    std::vector<uint32_t> order(all.size());
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        return cls[a] != cls[b] ? cls[a] < cls[b] : chunks[a] > chunks[b];
+    });
+    class_count[0] = class_count[1] = 0;
+    for (size_t k = 0; k < order.size(); k++) {
+        tiles[k] = all[order[k]];
+        class_count[cls[order[k]]]++;
+    }
+}
+
 }  // namespace czi
 
 using namespace czi;
@@ -692,7 +794,8 @@ int cz_tune(const char *key, int value)
     const struct { const char *name; std::atomic<uint64_t> *knob; uint64_t max; } host_knobs[] = {
         {"nacl_one_max", &g_nacl_one_bytes, czk_nacl_one_limit()},  // bytes; at least one pass of k_nacl_one
         {"fanout_min", &g_fanout_min, INT32_MAX}, {"fanout_short", &g_fanout_short, INT32_MAX},
-        {"fanout_split", &g_fanout_split, INT32_MAX}, {"fanin_short", &g_fanin_short, INT32_MAX}};
+        {"fanout_split", &g_fanout_split, INT32_MAX}, {"fanin_short", &g_fanin_short, INT32_MAX},
+        {"fanin_split", &g_fanin_split, INT32_MAX}};
     for (const auto &h : host_knobs)
         if (key && strcmp(key, h.name) == 0) {
             const int old = (int)h.knob->load(std::memory_order_relaxed);
@@ -1001,6 +1104,51 @@ int cz_open_fanin_runs(const cz_fanin_run *d_runs, uint32_t nruns, const cz_fano
     hipError_t e = czk_open_fanin_runs(d_runs, d_waves, class_count, region_stride, d_in, d_subs, d_subkeys, d_out,
                                        d_status, d_nonces, (hipStream_t)stream);
     return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_open_fanin_runs");
+}
+
+int cz_plan_fanin_split(const cz_fanin_run *h_runs, uint32_t nruns, const void *d_in, const void *d_out,
+                        uint32_t seg_blocks, cz_fanout_tile *h_tiles, uint32_t tile_cap, uint32_t *ntiles,
+                        uint32_t class_count[2], cz_fanout_join *h_joins, uint32_t join_cap, uint32_t *njoins,
+                        uint32_t *npart)
+{
+    if ((nruns && (!h_runs || !d_in || !d_out)) || !ntiles || !class_count || !njoins || !npart)
+        return fail(CZ_EINVAL, "cz_plan_fanin_split: null pointer");
+    if (int rc = check_fanin_runs(h_runs, nruns))
+        return rc;
+    if (seg_blocks == 0)
+        seg_blocks = fanin_split_seg_blocks(h_runs, nruns);
+    const FanoutSplitCounts c = fanin_split_counts(h_runs, nruns, seg_blocks);
+    // (tile, join and record indices are 32-bit; 0xffffffff in a tile's `part` means a body in one tile)
+    if (c.ntiles > 0xffffffffull || c.njoins > 0xffffffffull || c.npart > 0xffffffffull)
+        return fail(CZ_EINVAL, "cz_plan_fanin_split: more than 2^32 - 1 tiles, joins or partial records");
+    *ntiles = (uint32_t)c.ntiles;
+    *njoins = (uint32_t)c.njoins;
+    *npart = (uint32_t)c.npart;
+    if (c.ntiles > tile_cap || c.njoins > join_cap || (c.ntiles && !h_tiles) || (c.njoins && !h_joins))
+        return fail(CZ_EINVAL, "cz_plan_fanin_split: capacity too small (need %u tiles, %u joins)", *ntiles, *njoins);
+    plan_fanin_split(h_runs, nruns, d_in, seg_blocks, h_tiles, class_count, h_joins);
+    return CZ_OK;
+}
+
+int cz_open_fanin_split(const cz_fanin_run *d_runs, uint32_t nruns, const cz_fanout_tile *d_tiles,
+                        const uint32_t class_count[2], const cz_fanout_join *d_joins, uint32_t njoins,
+                        const void *d_in, const cz_fanin_sub *d_subs, const void *d_subkeys, void *d_out,
+                        void *d_work, uint16_t *d_status, uint64_t *d_nonces, void *stream)
+{
+    if (!class_count)
+        return fail(CZ_EINVAL, "cz_open_fanin_split: null pointer");
+    const uint64_t ntiles = (uint64_t)class_count[0] + class_count[1];
+    if (nruns == 0 || ntiles == 0)
+        return CZ_OK;
+    if (!d_runs || !d_tiles || !d_in || !d_subs || !d_subkeys || !d_out || !d_status)
+        return fail(CZ_EINVAL, "cz_open_fanin_split: null pointer");
+    if (njoins && (!d_joins || !d_work))
+        return fail(CZ_EINVAL, "cz_open_fanin_split: null join table / workspace");
+    if (ntiles > 0xffffffffull)
+        return fail(CZ_EINVAL, "cz_open_fanin_split: more than 2^32 - 1 tiles");
+    hipError_t e = czk_open_fanin_split(d_runs, d_tiles, class_count, d_joins, njoins, d_in, d_subs, d_subkeys, d_out,
+                                        d_work, d_status, d_nonces, (hipStream_t)stream);
+    return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_open_fanin_split");
 }
 
 int cz_seal_uniform_box(uint32_t count, uint32_t len, const void *d_box, uint64_t box_stride, void *d_out,

@@ -50,6 +50,25 @@ FanoutSplitCounts fanout_split_counts(const cz_fanout_run *runs, uint32_t nruns,
 void plan_fanout_split(const cz_fanout_run *runs, uint32_t nruns, const void *d_in, uint32_t seg_blocks,
                        cz_fanout_tile *tiles, uint32_t class_count[2], cz_fanout_join *joins);
 
+// The tables of a split fan-in open (cz_plan_fanin_split) for runs already validated and seg_blocks >= 1:
+// `tiles` / `joins` must hold fanin_split_counts(...).ntiles / .njoins records.
+uint32_t fanin_split();  // received runs of a full wave or more with payloads of at least this take the split fan-in (cz_tune "fanin_split")
+uint32_t fanin_split_seg_blocks(const cz_fanin_run *runs, uint32_t nruns);  // seg_blocks == 0
+FanoutSplitCounts fanin_split_counts(const cz_fanin_run *runs, uint32_t nruns, uint32_t seg_blocks);
+void plan_fanin_split(const cz_fanin_run *runs, uint32_t nruns, const void *d_in, uint32_t seg_blocks,
+                      cz_fanout_tile *tiles, uint32_t class_count[2], cz_fanout_join *joins);
+
+// Segment length for a received flush of `blocks` 64-byte blocks in all (cz_engine_flush_in learns its
+// frame sizes only from the parse): SEG_BLOCKS (128, the throughput setting) once
+// there are 64K lanes' worth, shorter below that (down to 4) so that a small flush spreads each frame
+// over many lanes instead of walking it on one (a 4 KiB frame alone: 65 blocks on one lane, ~150 us).
+// flush_out knows its lengths up front and uses batch_seg_blocks.
+inline uint32_t flush_seg_blocks(uint64_t blocks)
+{
+    const uint64_t s = (blocks + 65535) / 65536;
+    return (uint32_t)(s < 4 ? 4 : s > 128 ? 128 : s);
+}
+
 // segments, combine records and partial records the planner makes for one frame of `len` (payload for seal, body
 // for open) -- lets a caller size its buffers before planning
 inline void plan_counts(uint64_t len, int open, uint32_t seg_blocks, uint64_t &nseg, uint64_t &ncomb, uint64_t &npart)

@@ -3608,6 +3608,182 @@ __global__ __launch_bounds__(BLOCK) void k_open_combine(const cz_frame_desc *__r
     }
 }
 
+// Split fan-in open (cz_open_fanin_split): the lanes are (run, body, segment).  Wave w of this launch's
+// slice of the tile table serves bodies [first, first + 64) of run tiles[w].run on box blocks
+// [first_block, first_block + nblocks) of each.  The wave index goes through readfirstlane, so the tile
+// and run records are scalar loads and size, strides, bases, block range and chunk range are
+// wave-uniform: only the cz_fanin_sub record (key, floor, flags), the body and the output are per lane,
+// and what k_open_segments proves per wave by ballot -- a full wave of equal chunk counts -- holds here
+// by construction.  Every tile recomputes open_header for its lane, as every segment of
+// k_open_segments does; the tile with first_block 0 writes the nonce, rec[7] = early for the join, and
+// the status of a frame rejected before decryption.
+// ST_LINES: a full wave of 16-byte aligned bodies with no rejected lane takes a line emitter,
+// EmitSegLines where the run's slots and the tile's first output byte lie on 128-byte lines and
+// EmitShiftLines (any byte offset) otherwise -- the choice k_open_segments makes.  ST_DIRECT: lane-wise.
+// The class is a performance choice only: a wave of the line slice that is not full, whose bodies are
+// off 16-byte alignment or that holds a rejected lane opens lane-wise.  A rejected lane writes zeros
+// over its tile's chunk range itself.  The emitters clip their stores to the tile's own bytes, so the
+// tiles of one body and neighbouring bodies may share cache lines at any stride.  The tile that reaches
+// the end of the box zeroes [nout, out_stride) of its slot where the run owns its slots (owns_slots).
+// No workgroup barrier: the waves of a workgroup serve different runs and tiles.
+template <int ST>
+__global__ __launch_bounds__(BLOCK)
+__attribute__((amdgpu_waves_per_eu(ST == ST_LINES ? CZ_OPEN_SEG_WAVES_PER_EU : 1,
+                                   ST == ST_LINES ? CZ_OPEN_SEG_WAVES_PER_EU : 8))) void
+k_open_fanin_tiles(const cz_fanin_run *__restrict__ runs, const cz_fanout_tile *__restrict__ tiles, uint32_t ntiles,
+                   const uint8_t *__restrict__ in, const cz_fanin_sub *__restrict__ subs,
+                   const uint8_t *__restrict__ subkeys, uint8_t *__restrict__ out, u32 *__restrict__ work,
+                   uint16_t *__restrict__ status, uint64_t *__restrict__ nonces)
+{
+    static_assert(ST == ST_LINES || ST == ST_DIRECT, "two staging classes");
+    extern __shared__ uint4 smem[];
+    const u32 w = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES + (threadIdx.x >> 6));
+    if (w >= ntiles)
+        return;
+    const cz_fanout_tile tl = tiles[w];
+    const cz_fanin_run r = runs[tl.run];
+    const u32 size = r.size;
+    const u32 nblk = size ? (size + 63u) >> 6 : 1u;
+    if (tl.first >= r.count || tl.first_block >= nblk || tl.nblocks == 0u)
+        return;
+    const u32 lane = threadIdx.x & 63u;
+    const bool full_wave = r.count - tl.first >= 64u;
+    const bool live = lane < r.count - tl.first;
+    const u64 j = (u64)tl.first + (live ? lane : 0u);
+    const u64 idx = (u64)r.first_sub + j;
+    const cz_fanin_sub sb = subs[idx];
+    const uint8_t *in0 = in + r.in_off;
+    uint8_t *out0 = out + r.out_off;
+    const uint8_t *src = in0 + j * r.in_stride;
+    uint8_t *slot = out0 + j * r.out_stride;
+    long long floor = (long long)sb.floor;
+    if (sb.flags & CZ_FANIN_FLOOR_IS_BODY) {
+        const uint8_t *pb = in + sb.floor + 8;
+        if ((((uintptr_t)pb) & 7u) == 0) {
+            const uint2 pn = *reinterpret_cast<const uint2 *>(pb);
+            floor = (long long)(((u64)bswap32(pn.x) << 32) | (u64)bswap32(pn.y));
+        } else {
+            floor = (long long)read_be64(pb);
+        }
+    }
+    const bool check = (sb.flags & CZ_FANIN_CHECK_NONCE) != 0;
+    u32 n0 = 0, n1 = 0;
+    u64 nonce = 0;
+    const u32 early = open_header(src, size, check, floor, n0, n1, nonce);
+    const u32 b0 = tl.first_block;
+    const u32 b1 = tl.nblocks < nblk - b0 ? b0 + tl.nblocks : nblk;
+    u32 *rec = tl.part == 0xffffffffu ? nullptr : work + 16ull * ((u64)tl.part + (u64)lane * tl.nseg);
+    if (live && b0 == 0u) {
+        if (nonces)
+            nonces[idx] = nonce;
+        if (rec)
+            rec[7] = early;  // the join finishes bodies whose header passed
+        if (early != CZ_STATUS_OK)
+            status[idx] = (uint16_t)early;
+    }
+    // size < 33: every frame is COMMAND or MALFORMED and there is no payload
+    const bool has = size >= 33u;
+    const u32 nout = has ? size - 33u : 0u;
+    OpenSeg g{};
+    if (has)
+        g = open_seg_geom(size, b0, b1);
+    const u32 nch = g.ce - g.cb;
+    const u32 total = has ? (g.bend == g.nblk ? g.nout : 64u * g.ce) - 64u * g.cb : 0u;
+    uint8_t *dst = slot + 64ull * g.cb;
+    u32 key[8];
+    load_key(subkeys + 32ull * sb.key_idx, key);
+    u32 fl = 0;
+    bool done = false;
+    if constexpr (ST == ST_LINES) {
+        const bool in_al = ((((uintptr_t)in0) | r.in_stride) & 15u) == 0;
+        if (full_wave && in_al && nch != 0u && total <= SHIFT_TOTAL_MAX &&
+            __builtin_amdgcn_ballot_w64(early != CZ_STATUS_OK) == 0) {
+            uint8_t *wl = reinterpret_cast<uint8_t *>(smem) + (threadIdx.x >> 6) * SHIFT_LDS_BYTES;
+            u32 st;
+            if (((((uintptr_t)out0) | r.out_stride | (64u * g.cb)) & 127u) == 0) {
+                EmitSegLinesT<CZ_OPEN_ANY_STORE_CPOL> em{reinterpret_cast<uint4 *>(wl), dst, lane, total, 0u, 0u};
+                em.init(false);
+                st = open_segment<true>(src, size, key, n0, n1, b0, b1, rec, fl, em);
+            } else {  // plaintext at any byte offset
+                using EmS = EmitShiftLinesT<false, CZ_OPEN_ANY_STORE_CPOL>;
+                EmS em{wl, dst, lane, total, 0u, 0u};
+                em.init(false);
+                st = open_segment<true>(src, size, key, n0, n1, b0, b1, rec, fl, em);
+            }
+            if (!rec)
+                status[idx] = (uint16_t)(st | (st == CZ_STATUS_OK ? (fl << 8) : 0u));
+            done = true;
+        }
+    }
+    if (!live)
+        return;
+    if (!done) {
+        if (early != CZ_STATUS_OK) {
+            zero_bytes(dst, total);
+        } else {
+            u32 st;
+            if (ST == ST_DIRECT && aligned16(src, dst)) {
+                EmitDirect<true> em{dst, total};
+                st = open_segment<true>(src, size, key, n0, n1, b0, b1, rec, fl, em);
+            } else {
+                // (in the line slice: a table planned for other addresses -- correct, one path, not tuned)
+                EmitDirect<false> em{dst, total};
+                st = open_segment<false>(src, size, key, n0, n1, b0, b1, rec, fl, em);
+            }
+            if (!rec)
+                status[idx] = (uint16_t)(st | (st == CZ_STATUS_OK ? (fl << 8) : 0u));
+        }
+    }
+    if (b1 == nblk && r.out_stride > nout && owns_slots(r.out_stride))
+        zero_bytes(slot + nout, (u32)(r.out_stride - nout));
+}
+
+// The join of the split fan-in: one lane per (split run, body).  Wave w's record gives the run, the
+// wave's first body, lane 0's first partial record and the segments per body.  A body whose header was
+// rejected (R0[7]) is finished already; a bad tag zeroes what the tiles wrote, as k_open_combine.
+__global__ __launch_bounds__(BLOCK) void k_fanin_join(const cz_fanin_run *__restrict__ runs,
+                                                       const cz_fanout_join *__restrict__ joins, uint32_t njoins,
+                                                       const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                       const u32 *__restrict__ work, uint16_t *__restrict__ status)
+{
+    const u32 w = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES + (threadIdx.x >> 6));
+    if (w >= njoins)
+        return;
+    const cz_fanout_join jn = joins[w];
+    const cz_fanin_run r = runs[jn.run];
+    const u32 lane = threadIdx.x & 63u;
+    if (jn.first >= r.count || lane >= r.count - jn.first || jn.nseg == 0u || r.size < 33u)
+        return;
+    const u32 *R0 = work + 16ull * ((u64)jn.part + (u64)lane * jn.nseg);
+    if (R0[7] != CZ_STATUS_OK)
+        return;
+    const u64 j = (u64)jn.first + lane;
+    u32 tag[4];
+    combine_tag(R0, jn.nseg, tag);
+    const uint8_t *tp = in + r.in_off + j * r.in_stride + 16;
+    u32 tin[4];
+    for (int k = 0; k < 4; k++)
+        tin[k] = (u32)tp[4 * k] | ((u32)tp[4 * k + 1] << 8) | ((u32)tp[4 * k + 2] << 16) | ((u32)tp[4 * k + 3] << 24);
+    uint16_t *stp = status + (u64)r.first_sub + j;
+    if ((tag[0] ^ tin[0]) | (tag[1] ^ tin[1]) | (tag[2] ^ tin[2]) | (tag[3] ^ tin[3])) {
+        // never release unauthenticated plaintext: zero what the tiles wrote (16-byte stores over the
+        // aligned interior, bytes only at the edges)
+        uint8_t *dst = out + r.out_off + j * r.out_stride;
+        const u32 nout = r.size - 33u;
+        const u32 head = (u32)((16u - ((uintptr_t)dst & 15u)) & 15u);
+        u32 o = 0;
+        for (; o < head && o < nout; o++)
+            dst[o] = 0;
+        for (; o + 16u <= nout; o += 16u)
+            *reinterpret_cast<uint4 *>(dst + o) = make_uint4(0u, 0u, 0u, 0u);
+        for (; o < nout; o++)
+            dst[o] = 0;
+        *stp = CZ_STATUS_CRYPTO;
+    } else {
+        *stp = (uint16_t)(CZ_STATUS_OK | (R0[6] << 8));
+    }
+}
+
 
 // ---- ZMTP v2 framing (V2Encoder / V2Decoder) -------------------------------
 // One wave per item copies `size` bytes between arbitrary byte offsets: lane w
@@ -4369,6 +4545,38 @@ hipError_t czk_seal_fanout_split(const cz_fanout_run *runs, const cz_fanout_tile
     if (njoins)
         hipLaunchKernelGGL(k_fanout_join, dim3((njoins + WAVES - 1) / WAVES), dim3(BLOCK), 0, s, runs, joins, njoins,
                            (uint8_t *)out, (const u32 *)work);
+    return hipGetLastError();
+}
+
+// Split fan-in open: the tile table holds class_count[CZ_FANOUT_TILE_LINES] waves for the line
+// emitters, then class_count[CZ_FANOUT_TILE_DIRECT] lane-wise ones; the join runs after both -- at
+// most three launches whatever the number of runs, and no zero-pad launch.
+hipError_t czk_open_fanin_split(const cz_fanin_run *runs, const cz_fanout_tile *tiles, const uint32_t class_count[2],
+                                const cz_fanout_join *joins, uint32_t njoins, const void *in,
+                                const cz_fanin_sub *subs, const void *subkeys, void *out, void *work,
+                                uint16_t *status, uint64_t *nonces, hipStream_t s)
+{
+    static_assert(CZ_FANOUT_TILE_LINES == 0 && CZ_FANOUT_TILE_DIRECT == 1, "classes in table order");
+    uint32_t t0 = 0;
+    for (int cls = 0; cls < 2; t0 += class_count[cls++]) {
+        if (class_count[cls] == 0)
+            continue;
+        const Launch l = plan_fanin_tiles(cls, class_count[cls]);
+#define CZ_CASE(ST)                                                                                                   \
+    case ST:                                                                                                          \
+        hipLaunchKernelGGL(k_open_fanin_tiles<ST>, dim3(l.grid), dim3(BLOCK), l.lds, s, runs, tiles + t0,             \
+                           class_count[cls], (const uint8_t *)in, subs, (const uint8_t *)subkeys, (uint8_t *)out,     \
+                           (u32 *)work, status, nonces);                                                              \
+        break;
+        switch (l.st) {
+            CZ_CASE(ST_LINES) CZ_CASE(ST_DIRECT)
+        default: return hipErrorInvalidValue;
+        }
+#undef CZ_CASE
+    }
+    if (njoins)
+        hipLaunchKernelGGL(k_fanin_join, dim3((njoins + WAVES - 1) / WAVES), dim3(BLOCK), 0, s, runs, joins, njoins,
+                           (const uint8_t *)in, (uint8_t *)out, (const u32 *)work, status);
     return hipGetLastError();
 }
 

@@ -41,6 +41,11 @@ hipError_t czk_open_fanin_runs(const cz_fanin_run *runs, const cz_fanout_wave *w
                                void *out, uint16_t *status, uint64_t *nonces, hipStream_t s);
 // The staging class cz_plan_fanin gives the full waves of a run.  Host code, no device call.
 int czk_fanin_class(uint64_t out_stride, uint32_t size, uint32_t count, int aligned);
+// split fan-in open: lanes are (run, body, segment); tiles by class, then the join
+hipError_t czk_open_fanin_split(const cz_fanin_run *runs, const cz_fanout_tile *tiles, const uint32_t class_count[2],
+                                const cz_fanout_join *joins, uint32_t njoins, const void *in,
+                                const cz_fanin_sub *subs, const void *subkeys, void *out, void *work,
+                                uint16_t *status, uint64_t *nonces, hipStream_t s);
 
 // descriptor and segmented (ragged) batches
 hipError_t czk_seal_desc(const cz_frame_desc *desc, const uint32_t *order, uint32_t count, const void *in, void *out,

@@ -213,6 +213,13 @@ class CurveBatchEngine:
         plan: runs of at least 64 same-size frames with payloads up to cz_tune("fanin_short") bytes."""
         return int(self._L.cz_engine_fanin_frames(self._h))
 
+    @property
+    def fanin_split_frames(self):
+        """Frames of the last flush_in that the split fan-in open (cz_open_fanin_split) took out of the
+        segment plan: the other runs of at least 64 same-size frames with payloads of at least
+        cz_tune("fanin_split") bytes (0: the rule is off)."""
+        return int(self._L.cz_engine_fanin_split_frames(self._h))
+
     def messages_in(self, conn):
         cnt = ctypes.c_uint32()
         _lib.check(self._L.cz_engine_msgs_in(self._h, conn, ctypes.byref(cnt)), "cz_engine_msgs_in")
