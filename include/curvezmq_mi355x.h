@@ -615,6 +615,48 @@ typedef struct cz_v2_item {
 } cz_v2_item;
 int cz_v2_copy(const cz_v2_item *d_items, uint32_t count, const void *d_src, void *d_dst, void *stream);
 
+/* ---- 7b. device V2 scan: many received streams parsed where they lie ------------------------
+ * The decode half of section 7 for the many-connection shape: `count` received streams in device
+ * memory, one lane per stream walking its own header chain with cz_v2_parse's rules bit for bit
+ * (V2Decoder.java:37-105, Decoder.java:76-98), no frame capacity.  A stream is bytes
+ * [off, off + len) of d_wire at any byte alignment; headers are read with aligned dword loads that
+ * never touch a dword holding no byte of the stream. */
+typedef struct cz_v2_stream {        /* 32 bytes */
+    uint64_t off, len;               /* received bytes in d_wire */
+    uint64_t floor;                  /* cnPeerNonce: replay floor of the stream's first frame */
+    uint32_t key_idx, reserved;
+} cz_v2_stream;
+typedef struct cz_v2_stream_result { /* 32 bytes */
+    uint64_t consumed, slot_off;     /* bytes of the whole frames; where the stream's plaintext slots start */
+    uint32_t first, nframes;         /* the stream's frames are records [first, first + nframes) */
+    int32_t rc; uint32_t reserved;   /* CZ_OK / CZ_EPROTO / CZ_EMSGSIZE, as cz_v2_parse returns */
+} cz_v2_stream_result;
+typedef struct cz_v2_totals { uint64_t nframes, slot_bytes; } cz_v2_totals;
+/* Scan + placement (V2Decoder.java:37-105 / Decoder.java:76-98): per stream nframes, consumed and rc as
+ * cz_v2_parse gives them, and first / slot_off = the exclusive sums over the streams of nframes and of the
+ * plaintext slot bytes, sum of round_up(max(size - 33, 1), slot_align) with size - 33 taken as 0 below 33;
+ * *d_totals = the two sums.  slot_align: a power of two from 1 to 4096.  count == 0: CZ_OK, zero totals. */
+int cz_v2_scan(const cz_v2_stream *d_streams, uint32_t count, const void *d_wire, int64_t maxmsgsize,
+               uint32_t slot_align, cz_v2_stream_result *d_results, cz_v2_totals *d_totals, void *stream);
+/* Emit (the frames V2Decoder.java:37-105 / Decoder.java:76-98 would hand on): repeats the walk over the
+ * frames d_results counted and writes, for frame k of stream s at index first + k, a cz_v2_frame {body_off
+ * relative to the stream, size, msg_flags} and / or the open's descriptor {in_off = off + body_off, out_off =
+ * its slot, len = size, key_idx, counter = floor, flags = CZ_DESC_CHECK_NONCE, prev = k ? index - 1 : -1}.
+ * Nothing is written at or past first + nframes.  Either output may be NULL. */
+int cz_v2_scan_emit(const cz_v2_stream *d_streams, const cz_v2_stream_result *d_results, uint32_t count,
+                    const void *d_wire, uint32_t slot_align, cz_v2_frame *d_frames, cz_frame_desc *d_desc,
+                    void *stream);                       /* either output may be NULL */
+/* V2Decoder.java:37-105 / Decoder.java:76-98 + Mechanism.decode for every whole frame of every stream:
+ * scan, read the totals (one synchronisation), emit, cz_open_batch from the wire bytes where they lie.
+ * CZ_ENOMEM with *h_totals filled and nothing opened when the totals exceed desc_cap / out_cap;
+ * CZ_EINVAL above 2^31 - 1 frames.  d_status / d_nonces (optional) hold desc_cap records.  A frame's
+ * replay floor is read at bytes [8, 16) of the frame before it even when that frame is shorter, so
+ * d_wire must be readable for 16 bytes past its last stream. */
+int cz_open_streams(const cz_v2_stream *d_streams, uint32_t count, const void *d_wire, int64_t maxmsgsize,
+                    uint32_t slot_align, cz_v2_stream_result *d_results, cz_frame_desc *d_desc, uint64_t desc_cap,
+                    void *d_out, uint64_t out_cap, const void *d_subkeys, uint16_t *d_status, uint64_t *d_nonces,
+                    cz_v2_totals *h_totals, void *stream);
+
 /* ---- 8. batching engine: many CURVE connections, one device batch per flush -----------------
  * The GPU form of StreamEngine's encode/decode loops (outEvent: pull + mechanism.encode +
  * V2Encoder up to OUT_BATCH_SIZE, StreamEngine.java:467-535; inEvent: V2Decoder +
@@ -690,6 +732,14 @@ int cz_engine_flush_in(cz_engine *e);
 uint64_t cz_engine_fanin_frames(const cz_engine *e);
 /* ... and that its cz_open_fanin_split calls opened */
 uint64_t cz_engine_fanin_split_frames(const cz_engine *e);
+/* Scanned flush (section 7b), cz_tune("scan_in") = n > 0 bytes: a flush in which at least 64 live connections
+ * have received bytes and every one of them holds at most n takes no host parse at all.  The received bytes
+ * go over as in any flush, one 32-byte cz_v2_stream per connection follows, the device scans and places them,
+ * the totals come back (the flush's one extra synchronisation), and cz_v2_scan_emit's descriptors open every
+ * frame from the wire bytes where they lie: no unpacking copy, no per-frame metadata upload, no segment plan
+ * and no fan-in routing.  Always one group.  Delivered messages, cnPeerNonce, errors and events are those of
+ * the unscanned flush.  Frames of the last cz_engine_flush_in opened this way (0: the path was not taken): */
+uint64_t cz_engine_scan_frames(const cz_engine *e);
 /* decoded messages of the last cz_engine_flush_in (pinned memory, valid until the next one) */
 int cz_engine_msgs_in(cz_engine *e, int conn, uint32_t *count);
 int cz_engine_msg_in(cz_engine *e, int conn, uint32_t i, const uint8_t **payload, uint32_t *len, int *msg_flags);
@@ -974,7 +1024,15 @@ int cz_device_ok(void);
  *              against 0.0597 ms for 16 runs of 1024 bodies; 16 KiB: 0.1850 against 0.1865 ms) and the routed flush at
  *              all 8 (1 KiB x 16: 2.03 against 3.39 ms; 64 KiB x 256: 368.8 against 370.3 ms), but 64 KiB loses one
  *              shape (16 runs of 1024 bodies: 0.6197 against 0.6033 ms), so no length qualifies.  A caller whose runs
- *              stay below 64 KiB can set 1024; profiles/fanin/fanin_split.json */
+ *              stay below 64 KiB can set 1024; profiles/fanin/fanin_split.json
+ *   "scan_in": cz_engine_flush_in parses on the device (section 7b, cz_engine_scan_frames) when at least 64 live
+ *              connections have received bytes and each holds at most this many; 0 = off.  Default 0, by the rule that set fanin_short: the largest
+ *              measured per-connection byte count at which the scanned flush is not slower than the unscanned one at every
+ *              measured shape at or below it.  The smallest shape already loses (1024 connections x 16 frames of 100 B,
+ *              2160 bytes each: 1.545 against 1.440 ms; 64 x one 4 KiB frame: 0.307 against 0.186 ms; 16 x 256 B: 1.572
+ *              against 1.502 ms): the host parse it removes ran behind the H2D, the totals read-back does not.  It wins
+ *              at 16 x 1 KiB (1.822 against 2.825 ms) and 16 x 4 KiB (2.945 against 3.588 ms); a caller whose flushes are
+ *              a thousand connections with such frames can set 65536; profiles/scan/scan.json */
 int cz_tune(const char *key, int value);
 
 #ifdef __cplusplus

@@ -81,6 +81,23 @@ class cz_v2_item(ctypes.Structure):
 assert ctypes.sizeof(cz_v2_frame) == 16 and ctypes.sizeof(cz_v2_item) == 24
 
 
+class cz_v2_stream(ctypes.Structure):
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint64), ("floor", ctypes.c_uint64),
+                ("key_idx", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class cz_v2_stream_result(ctypes.Structure):
+    _fields_ = [("consumed", ctypes.c_uint64), ("slot_off", ctypes.c_uint64), ("first", ctypes.c_uint32),
+                ("nframes", ctypes.c_uint32), ("rc", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
+
+
+class cz_v2_totals(ctypes.Structure):
+    _fields_ = [("nframes", ctypes.c_uint64), ("slot_bytes", ctypes.c_uint64)]
+
+
+assert ctypes.sizeof(cz_v2_stream) == 32 and ctypes.sizeof(cz_v2_stream_result) == 32 and ctypes.sizeof(cz_v2_totals) == 16
+
+
 class cz_fanout_sub(ctypes.Structure):
     _fields_ = [("counter", ctypes.c_uint64), ("key_idx", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
@@ -197,6 +214,9 @@ SIGNATURES = {
     "cz_v2_header_size": (_U32, [_U64]),
     "cz_v2_parse": (_I, [_VP, _U64, ctypes.c_int64, _VP, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U64)]),
     "cz_v2_copy": (_I, [_VP, _U32, _VP, _VP, _VP]),
+    "cz_v2_scan": (_I, [_VP, _U32, _VP, ctypes.c_int64, _U32, _VP, _VP, _VP]),
+    "cz_v2_scan_emit": (_I, [_VP, _VP, _U32, _VP, _U32, _VP, _VP, _VP]),
+    "cz_open_streams": (_I, [_VP, _U32, _VP, ctypes.c_int64, _U32, _VP, _VP, _U64, _VP, _U64, _VP, _VP, _VP, _VP, _VP]),
     "cz_engine_create": (_I, [ctypes.POINTER(_VP), _U64, _I]),
     "cz_engine_destroy": (None, [_VP]),
     "cz_engine_add_conn": (_I, [_VP, _I, _VP, _U64, _U64]),
@@ -218,6 +238,7 @@ SIGNATURES = {
     "cz_engine_peer_nonce": (_U64, [_VP, _I]),
     "cz_engine_fanin_frames": (_U64, [_VP]),
     "cz_engine_fanin_split_frames": (_U64, [_VP]),
+    "cz_engine_scan_frames": (_U64, [_VP]),
     "cz_scalarmult": (_I, [_VP, _VP, _VP]),
     "cz_box_keypair": (_I, [_VP, _VP]),
     "cz_box_beforenm": (_I, [_VP, _VP, _VP]),

@@ -417,6 +417,34 @@ def open_batch(desc, count, inp, out, subkeys_t, status, nonces=None, order=None
                                         _ptr(status), _ptr(nonces), _stream(stream)), "cz_open_batch")
 
 
+def open_streams(streams, wire, results, desc, out, subkeys_t, status, nonces=None, maxmsgsize=-1, slot_align=128,
+                 desc_cap=None, out_cap=None, stream=None):
+    """Parse and open many received streams where they lie (cz_open_streams): `streams` a device tensor of
+    wire.V2_STREAM_DTYPE records, `wire` the received bytes (readable for 16 bytes past the last stream),
+    `results` / `desc` / `status` / `nonces` device tensors for one record per stream / frame, `out` the
+    plaintext slots.  Scan, one synchronisation for the totals, emit, open.  Returns (rc, nframes,
+    slot_bytes): rc is CZ_OK, or CZ_ENOMEM with the totals filled and nothing opened when they exceed
+    desc_cap / out_cap (default: what `desc` / `out` hold).  Any other failure raises."""
+    from .wire import V2_STREAM_DTYPE
+    _need_cuda_u8(wire, "wire")
+    _need_cuda_u8(out, "out")
+    count = streams.numel() // V2_STREAM_DTYPE.itemsize
+    if desc_cap is None:
+        desc_cap = desc.numel() * desc.element_size() // DESC_DTYPE.itemsize
+    if out_cap is None:
+        out_cap = out.numel()
+    if status.numel() * status.element_size() < 2 * desc_cap or (
+            nonces is not None and nonces.numel() * nonces.element_size() < 8 * desc_cap):
+        raise ValueError("status / nonces hold fewer than desc_cap records")
+    tot = _lib.cz_v2_totals()
+    rc = _lib.lib().cz_open_streams(_ptr(streams), count, _ptr(wire), maxmsgsize, slot_align, _ptr(results), _ptr(desc),
+                                    desc_cap, _ptr(out), out_cap, _ptr(subkeys_t), _ptr(status), _ptr(nonces),
+                                    ctypes.byref(tot), _stream(stream))
+    if rc != _lib.CZ_ENOMEM:
+        _lib.check(rc, "cz_open_streams")
+    return rc, int(tot.nframes), int(tot.slot_bytes)
+
+
 def fill(buf, seed, stream=None):
     """Counter-based SplitMix64 synthetic bytes (tests/cz_testlib.py splitmix_words)."""
     _lib.check(_lib.lib().cz_fill(_ptr(buf), buf.numel() * buf.element_size(), seed, _stream(stream)), "cz_fill")

@@ -259,6 +259,10 @@ struct cz_engine {
     uint32_t pub_seq = 0;  // id of the last cz_engine_publish call (OutMsg::pub)
     uint64_t fanin_frames = 0;  // frames of the last flush_in that its cz_open_fanin_runs calls opened
     uint64_t fanin_split_frames = 0;  // ... and that its cz_open_fanin_split calls opened
+    uint64_t scan_frames = 0;  // ... and that the scanned path opened (cz_tune "scan_in": the whole flush or nothing)
+    // scanned flush: one cz_v2_stream per receiving connection, its cz_v2_stream_result, then the totals record
+    DevBuf d_scan;
+    HostBuf h_scan;
     HostBuf h_status, h_nonces;
     HostBuf h_meta;  // pinned staging of descriptors / items / segment lists (async H2D)
     RxPool rxpool;   // every connection's receive buffer
@@ -292,9 +296,9 @@ struct cz_engine {
             }
         for (DevBuf *b : {&subkeys, &d_in, &d_body, &d_wire, &d_desc, &d_seg, &d_comb, &d_work, &d_items, &d_status,
                           &d_nonces, &d_plain, &d_subs, &d_fruns, &d_fwaves, &d_ftiles, &d_fjoins,
-                          &d_fwork, &d_stage})
+                          &d_fwork, &d_stage, &d_scan})
             b->release();
-        for (HostBuf *b : {&arena, &h_wire, &h_plain, &h_status, &h_nonces, &h_meta, &h_stage})
+        for (HostBuf *b : {&arena, &h_wire, &h_plain, &h_status, &h_nonces, &h_meta, &h_stage, &h_scan})
             b->release();
     }
 
@@ -623,6 +627,7 @@ struct cz_engine {
         in_msgs.clear();
         fanin_frames = 0;
         fanin_split_frames = 0;
+        scan_frames = 0;
         for (Conn &c : conns)
             c.in_msgs.clear();
         // 0. the live connections, in groups of ~equal received bytes
@@ -642,6 +647,12 @@ struct cz_engine {
             parsed.push_back({(uint32_t)ci, 0u, 0u, 0u, 0u, 0});
             rx_total += c.rx_len;
         }
+        // The scanned flush (cz_tune "scan_in" = n > 0): at least one full wave of connections, none holding more
+        // than n bytes -- which bounds a lane's header walk and the longest frame one lane may have to open.
+        const uint32_t scan_n = scan_in();
+        bool scanned = scan_n && parsed.size() >= 64;
+        for (size_t q = 0; scanned && q < parsed.size(); q++)
+            scanned = conns[parsed[q].conn].rx_len <= scan_n;
         const uint32_t seg = flush_seg_blocks(rx_total / 64);
         struct Group {
             size_t pa, pb;        // parsed[pa, pb)
@@ -650,7 +661,7 @@ struct cz_engine {
         };
         std::vector<Group> groups;
         {
-            const int G = rx_total >= (64ull << 20) ? CZ_ENGINE_GROUPS : 1;
+            const int G = rx_total >= (64ull << 20) && !scanned ? CZ_ENGINE_GROUPS : 1;  // (scanned: always one)
             size_t pa = 0;
             uint64_t acc = 0;
             for (size_t q = 0; q < parsed.size(); q++) {
@@ -721,7 +732,8 @@ struct cz_engine {
                 }
                 span_end[gi] = spans.size();
             }
-            if (off && (e = d_wire.reserve(off)) != hipSuccess)
+            // (scanned: the open reads a frame's replay floor at bytes [8, 16) of the frame before it where they lie)
+            if (off && (e = d_wire.reserve(off + (scanned ? 16 : 0))) != hipSuccess)
                 return hip_fail(e, "cz_engine: alloc");
         }
         for (size_t gi = 0, si = 0; gi < groups.size(); gi++) {
@@ -835,7 +847,74 @@ struct cz_engine {
                     plan_counts(f.size, 1, seg, w.nseg, w.ncomb, w.npart);
             }
         };
-        {
+        if (scanned) {
+            // 1s. The scanned flush, on the one stream of a one-group flush: a 32-byte record per connection
+            //     goes up, the device walks every connection's headers (one lane each) and places the streams,
+            //     and the totals come back with the per-stream results -- the one extra synchronisation, which
+            //     sizes the buffers.  Then the emitted descriptors open every frame from d_wire itself.  What
+            //     comes back fills exactly what the host parse and build fill below: Parsed, the descriptors
+            //     (for out_off / len), statuses and nonces.
+            const uint32_t ns = (uint32_t)parsed.size();
+            const uint64_t o_res = (uint64_t)ns * sizeof(cz_v2_stream),
+                           o_tot = o_res + (uint64_t)ns * sizeof(cz_v2_stream_result);
+            if ((e = h_scan.reserve(o_tot + sizeof(cz_v2_totals))) != hipSuccess ||
+                (e = d_scan.reserve(o_tot + sizeof(cz_v2_totals))) != hipSuccess)
+                return hip_fail(e, "cz_engine: alloc");
+            cz_v2_stream *h_streams = (cz_v2_stream *)h_scan.ptr;
+            for (uint32_t q = 0; q < ns; q++) {
+                const Conn &c = conns[parsed[q].conn];
+                h_streams[q] = {parsed[q].rx_off, c.rx_len, c.peer_nonce, c.rx_key, 0u};
+            }
+            const cz_v2_stream *d_streams = (const cz_v2_stream *)d_scan.ptr;
+            cz_v2_stream_result *d_res = (cz_v2_stream_result *)((uint8_t *)d_scan.ptr + o_res);
+            const cz_v2_stream_result *h_res = (const cz_v2_stream_result *)((const uint8_t *)h_scan.ptr + o_res);
+            const cz_v2_totals *h_tot = (const cz_v2_totals *)((const uint8_t *)h_scan.ptr + o_tot);
+            if ((e = hipMemcpyAsync(d_scan.ptr, h_streams, o_res, hipMemcpyHostToDevice, qk)) != hipSuccess ||
+                (e = czk_v2_scan(d_streams, ns, d_wire.ptr, -1, (uint32_t)SLOT_ALIGN, d_res,
+                                 (cz_v2_totals *)((uint8_t *)d_scan.ptr + o_tot), qk)) != hipSuccess ||
+                (e = hipMemcpyAsync((uint8_t *)h_scan.ptr + o_res, d_res, o_tot + sizeof(cz_v2_totals) - o_res,
+                                    hipMemcpyDeviceToHost, qk)) != hipSuccess ||
+                (e = hipStreamSynchronize(qk)) != hipSuccess) {
+                drain();
+                return hip_fail(e, "cz_engine: flush_in scan");
+            }
+            pt.mark("scan");
+            if (h_tot->nframes > 0x7fffffffull)
+                return fail(CZ_EINVAL, "cz_engine: more than 2^31 - 1 received frames in one flush");
+            const uint32_t sn = (uint32_t)h_tot->nframes;
+            const uint64_t spl = h_tot->slot_bytes;
+            if (sn) {
+                if ((e = d_plain.reserve(spl)) != hipSuccess || (e = d_status.reserve((uint64_t)sn * 2)) != hipSuccess ||
+                    (e = d_nonces.reserve((uint64_t)sn * 8)) != hipSuccess ||
+                    (e = d_desc.reserve((uint64_t)sn * sizeof(cz_frame_desc))) != hipSuccess ||
+                    (e = h_plain.reserve(spl)) != hipSuccess || (e = h_status.reserve((uint64_t)sn * 2)) != hipSuccess ||
+                    (e = h_nonces.reserve((uint64_t)sn * 8)) != hipSuccess ||
+                    (e = h_meta.reserve((uint64_t)sn * sizeof(cz_frame_desc))) != hipSuccess)
+                    return hip_fail(e, "cz_engine: alloc");
+                // (the descriptors land at the start of the metadata staging, where the delivery step reads them)
+                if ((e = czk_v2_emit(d_streams, d_res, ns, d_wire.ptr, (uint32_t)SLOT_ALIGN, nullptr,
+                                     (cz_frame_desc *)d_desc.ptr, qk)) != hipSuccess ||
+                    (e = czk_open_desc((const cz_frame_desc *)d_desc.ptr, nullptr, sn, d_wire.ptr, d_plain.ptr, subkeys.ptr,
+                                       (uint16_t *)d_status.ptr, (uint64_t *)d_nonces.ptr, qk)) != hipSuccess ||
+                    (e = hipMemcpyAsync(h_plain.ptr, d_plain.ptr, spl, hipMemcpyDeviceToHost, qk)) != hipSuccess ||
+                    (e = hipMemcpyAsync(h_status.ptr, d_status.ptr, (uint64_t)sn * 2, hipMemcpyDeviceToHost, qk)) !=
+                        hipSuccess ||
+                    (e = hipMemcpyAsync(h_nonces.ptr, d_nonces.ptr, (uint64_t)sn * 8, hipMemcpyDeviceToHost, qk)) !=
+                        hipSuccess ||
+                    (e = hipMemcpyAsync(h_meta.ptr, d_desc.ptr, (uint64_t)sn * sizeof(cz_frame_desc),
+                                        hipMemcpyDeviceToHost, qk)) != hipSuccess) {
+                    drain();
+                    return hip_fail(e, "cz_engine: flush_in");
+                }
+            }
+            for (uint32_t q = 0; q < ns; q++) {
+                parsed[q].first = h_res[q].first;
+                parsed[q].count = h_res[q].nframes;
+                parsed[q].consumed = h_res[q].consumed;
+                parsed[q].perr = h_res[q].rc;
+            }
+            scan_frames = sn;
+        } else {
             std::vector<std::thread> th;
             for (size_t gi = 1; gi < groups.size(); gi++)
                 th.emplace_back(parse, gi);
@@ -1679,6 +1758,7 @@ uint64_t cz_engine_peer_nonce(cz_engine *e, int conn)
 }
 
 uint64_t cz_engine_fanin_frames(const cz_engine *e) { return e ? e->fanin_frames : 0; }
+uint64_t cz_engine_scan_frames(const cz_engine *e) { return e ? e->scan_frames : 0; }
 uint64_t cz_engine_fanin_split_frames(const cz_engine *e) { return e ? e->fanin_split_frames : 0; }
 
 }  // extern "C"

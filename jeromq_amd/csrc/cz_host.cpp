@@ -324,6 +324,24 @@ static std::atomic<uint64_t> g_fanin_split{0};
 
 uint32_t fanin_split() { return (uint32_t)g_fanin_split.load(std::memory_order_relaxed); }
 
+// cz_engine_flush_in: a flush in which at least 64 live connections have received bytes and every one of
+// them holds at most this many bytes is parsed on the device (cz_v2_scan) and opened from the wire bytes
+// where they lie; 0 = off (cz_tune "scan_in").
+// Default 0, by the rule that set fanin_short: the largest measured per-connection byte count at which the scanned
+// flush is not slower in the median than the unscanned flush of the same process, at every measured shape at or
+// below it (tools/scan_bench.py, profiles/scan/scan.json, medians of 7, legs interleaved):
+//   connections x frames x len   bytes per connection   flush_in ms, scanned / unscanned
+//   1024 x 16 x 100              2160                   1.545 / 1.440
+//   64 x 1 x 4096                4138                   0.307 / 0.186   (one lane per 4 KiB frame)
+//   1024 x 16 x 256              4768                   1.572 / 1.502
+//   1024 x 16 x 1024             17056                  1.822 / 2.825
+//   1024 x 16 x 4096             66208                  2.945 / 3.588
+// The smallest shape loses, so no byte count qualifies: the host parse the scan removes ran behind the H2D of the
+// received bytes, while the totals read-back and the descriptor D2H are on the critical path.
+static std::atomic<uint64_t> g_scan_in{0};
+
+uint32_t scan_in() { return (uint32_t)g_scan_in.load(std::memory_order_relaxed); }
+
 // NaCl box/open of one message on the device.  A MESSAGE is the NaCl box of
 // 0^32 || flags || payload, so m[32] rides as the flags byte and m[33:] as the payload; for open
 // the 16 bytes ahead of the tag are rebuilt as "\x07MESSAGE" || n[16:24] and the nonce check is off.
@@ -795,7 +813,7 @@ int cz_tune(const char *key, int value)
         {"nacl_one_max", &g_nacl_one_bytes, czk_nacl_one_limit()},  // bytes; at least one pass of k_nacl_one
         {"fanout_min", &g_fanout_min, INT32_MAX}, {"fanout_short", &g_fanout_short, INT32_MAX},
         {"fanout_split", &g_fanout_split, INT32_MAX}, {"fanin_short", &g_fanin_short, INT32_MAX},
-        {"fanin_split", &g_fanin_split, INT32_MAX}};
+        {"fanin_split", &g_fanin_split, INT32_MAX}, {"scan_in", &g_scan_in, INT32_MAX}};
     for (const auto &h : host_knobs)
         if (key && strcmp(key, h.name) == 0) {
             const int old = (int)h.knob->load(std::memory_order_relaxed);

@@ -58,6 +58,8 @@ FanoutSplitCounts fanin_split_counts(const cz_fanin_run *runs, uint32_t nruns, u
 void plan_fanin_split(const cz_fanin_run *runs, uint32_t nruns, const void *d_in, uint32_t seg_blocks,
                       cz_fanout_tile *tiles, uint32_t class_count[2], cz_fanout_join *joins);
 
+uint32_t scan_in();  // a flush of at least 64 receiving connections with at most this many bytes each is parsed on the device (cz_tune "scan_in")
+
 // Segment length for a received flush of `blocks` 64-byte blocks in all (cz_engine_flush_in learns its
 // frame sizes only from the parse): SEG_BLOCKS (128, the throughput setting) once
 // there are 64K lanes' worth, shorter below that (down to 4) so that a small flush spreads each frame

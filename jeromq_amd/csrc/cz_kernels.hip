@@ -3862,6 +3862,204 @@ __global__ __launch_bounds__(BLOCK) void k_v2_copy(const cz_v2_item *__restrict_
     }
 }
 
+// ---- device V2 scan (cz_v2_scan / cz_v2_scan_emit): one lane per received stream -------------
+// The decode half of the framing for many short streams: lane s walks the header chain of stream s
+// with cz_v2_parse's rules (V2Decoder.java:37-105, Decoder.java:76-98).  Nothing is speculative --
+// a lane only ever follows its own chain -- and lanes of a wave differ in trip count, so the loop
+// body is one header: three clamped aligned dword loads (ld_dw_clamped: no dword without a byte of
+// the stream is touched) funnelled by the header's byte phase, the size checks, one add.
+struct V2Stream {
+    const uint8_t *sbase;  // the aligned dword holding the stream's first byte
+    u32 r0;                // the first byte's place in it
+    intptr_t hi;           // the last dword holding a byte of the stream, relative to sbase
+    u64 len;
+};
+
+__device__ __forceinline__ V2Stream v2_stream(const uint8_t *__restrict__ wire, const cz_v2_stream &st)
+{
+    const uintptr_t s0 = (uintptr_t)(wire + st.off);
+    V2Stream v;
+    v.sbase = reinterpret_cast<const uint8_t *>(s0 & ~(uintptr_t)3);
+    v.r0 = (u32)(s0 & 3u);
+    v.len = st.len;
+    v.hi = st.len ? (intptr_t)(((s0 + st.len - 1u) & ~(uintptr_t)3) - (s0 & ~(uintptr_t)3)) : 0;
+    return v;
+}
+
+// The header at stream byte p < len: the flags byte, the 1-byte size and the BE64 size (valid when
+// the stream holds 2 / 9 bytes from p on; the caller checks that before it uses either).
+__device__ __forceinline__ void v2_header(const V2Stream &v, u64 p, u32 &flags, u32 &size1, u64 &size8)
+{
+    const u64 x = p + v.r0;
+    const intptr_t j = (intptr_t)(x & ~(u64)3);
+    const u32 r = (u32)(x & 3u);
+    const u32 d0 = ld_dw_clamped(v.sbase, 0, v.hi, j);
+    const u32 d1 = ld_dw_clamped(v.sbase, 0, v.hi, j + 4);
+    const u32 d2 = ld_dw_clamped(v.sbase, 0, v.hi, j + 8);
+    const u32 b0 = funnel(d1, d0, r);   // header bytes 0..3
+    const u32 b1 = funnel(d2, d1, r);   // 4..7
+    const u32 b8 = (d2 >> (8u * r)) & 0xffu;
+    flags = b0 & 0xffu;
+    size1 = (b0 >> 8) & 0xffu;
+    // Wire.getUInt64: big-endian bytes 1..8
+    size8 = ((u64)__builtin_bswap32((b0 >> 8) | (b1 << 24)) << 32) | __builtin_bswap32((b1 >> 8) | (b8 << 24));
+}
+
+// One step of the walk at p < len: 0 = a whole frame (h, size set), 1 = the stream ends inside this
+// frame, else the error of a bad header.
+__device__ __forceinline__ int v2_step(const V2Stream &v, u64 p, long long maxmsgsize, u32 &flags, u32 &h, u64 &size)
+{
+    u32 size1;
+    u64 size8;
+    v2_header(v, p, flags, size1, size8);
+    const u64 left = v.len - p;
+    if (flags & CZ_V2_LARGE) {
+        if (left < 9u)
+            return 1;
+        size = size8;
+        h = 9u;
+        if ((long long)size <= 0)  // V2Decoder.eightByteSizeReady
+            return CZ_EPROTO;
+    } else {
+        if (left < 2u)
+            return 1;
+        size = size1;
+        h = 2u;
+    }
+    if ((maxmsgsize >= 0 && size > (u64)maxmsgsize) || size > 0x7fffffffull)  // Decoder.sizeReady
+        return CZ_EMSGSIZE;
+    return left - h < size ? 1 : 0;
+}
+
+// the engine's plaintext slot of a body of `size` bytes; amask = slot_align - 1
+__device__ __forceinline__ u64 v2_slot(u64 size, u64 amask)
+{
+    const u64 plen = size > 33u ? size - 33u : 0u;
+    return ((plen ? plen : 1u) + amask) & ~amask;
+}
+
+// results[s] = {consumed, the stream's slot bytes (k_v2_place turns them into slot_off), 0, nframes, rc}
+__global__ __launch_bounds__(BLOCK) void k_v2_scan(const cz_v2_stream *__restrict__ streams, uint32_t count,
+                                                    const uint8_t *__restrict__ wire, long long maxmsgsize,
+                                                    uint32_t slot_align, cz_v2_stream_result *__restrict__ results)
+{
+    const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
+    if (s >= count)
+        return;
+    const V2Stream v = v2_stream(wire, streams[s]);
+    const u64 amask = (u64)slot_align - 1u;
+    u64 p = 0, slots = 0;
+    u32 nf = 0;
+    int rc = CZ_OK;
+    while (p < v.len) {
+        u32 flags, h;
+        u64 size;
+        const int step = v2_step(v, p, maxmsgsize, flags, h, size);
+        if (step) {
+            rc = step == 1 ? CZ_OK : step;
+            break;
+        }
+        nf++;
+        p += h + size;
+        slots += v2_slot(size, amask);
+    }
+    cz_v2_stream_result res;
+    res.consumed = p;
+    res.slot_off = slots;
+    res.first = 0;
+    res.nframes = nf;
+    res.rc = rc;
+    res.reserved = 0;
+    results[s] = res;
+}
+
+// Placement: first / slot_off = the exclusive sums over the streams of nframes / slot bytes, and the
+// totals record.  One workgroup: thread t sums its own contiguous share of the streams, the 256
+// partial sums are scanned in LDS, and each thread walks its share again.  (At the stream counts
+// this path serves -- tens of thousands -- the whole table lies in L2 and the launch costs more
+// than the walk; a multi-workgroup scan would add a second launch for nothing.)
+__global__ __launch_bounds__(BLOCK) void k_v2_place(cz_v2_stream_result *__restrict__ results, uint32_t count,
+                                                     cz_v2_totals *__restrict__ totals)
+{
+    __shared__ u64 sn[BLOCK], sb[BLOCK];
+    const u32 t = threadIdx.x;
+    const u64 per = ((u64)count + BLOCK - 1) / BLOCK;
+    const u64 a = (u64)t * per < count ? (u64)t * per : count, b = a + per < count ? a + per : count;
+    u64 n = 0, bytes = 0;
+    for (u64 i = a; i < b; i++) {
+        n += results[i].nframes;
+        bytes += results[i].slot_off;
+    }
+    sn[t] = n;
+    sb[t] = bytes;
+    __syncthreads();
+    for (u32 d = 1; d < (u32)BLOCK; d <<= 1) {
+        const u64 xn = t >= d ? sn[t - d] : 0u, xb = t >= d ? sb[t - d] : 0u;
+        __syncthreads();
+        sn[t] += xn;
+        sb[t] += xb;
+        __syncthreads();
+    }
+    if (t == (u32)BLOCK - 1u) {
+        totals->nframes = sn[t];
+        totals->slot_bytes = sb[t];
+    }
+    u64 n0 = sn[t] - n, b0 = sb[t] - bytes;
+    for (u64 i = a; i < b; i++) {
+        const u32 nf = results[i].nframes;
+        const u64 sz = results[i].slot_off;
+        results[i].first = (u32)n0;
+        results[i].slot_off = b0;
+        n0 += nf;
+        b0 += sz;
+    }
+}
+
+// Emit: the walk again over the frames the scan counted (so no size checks: they passed), writing
+// frame k of stream s at index first + k.  The walk also stops at the stream's end, so results that
+// do not belong to these streams cannot lead a load outside them.
+__global__ __launch_bounds__(BLOCK) void k_v2_emit(const cz_v2_stream *__restrict__ streams,
+                                                    const cz_v2_stream_result *__restrict__ results, uint32_t count,
+                                                    const uint8_t *__restrict__ wire, uint32_t slot_align,
+                                                    cz_v2_frame *__restrict__ frames, cz_frame_desc *__restrict__ desc)
+{
+    const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
+    if (s >= count)
+        return;
+    const cz_v2_stream st = streams[s];
+    const cz_v2_stream_result res = results[s];
+    const V2Stream v = v2_stream(wire, st);
+    const u64 amask = (u64)slot_align - 1u;
+    u64 p = 0, slot = res.slot_off;
+    for (u32 k = 0; k < res.nframes && p < v.len; k++) {
+        u32 flags, h;
+        u64 size;
+        if (v2_step(v, p, -1, flags, h, size))
+            break;
+        const u64 i = (u64)res.first + k;
+        if (frames) {
+            cz_v2_frame f;
+            f.body_off = p + h;
+            f.size = (u32)size;
+            f.msg_flags = ((flags & CZ_V2_MORE) ? CZ_MSG_MORE : 0u) | ((flags & CZ_V2_COMMAND) ? CZ_MSG_COMMAND : 0u);
+            frames[i] = f;
+        }
+        if (desc) {
+            cz_frame_desc d;
+            d.in_off = st.off + p + h;
+            d.out_off = slot;
+            d.len = (u32)size;
+            d.key_idx = st.key_idx;
+            d.counter = st.floor;
+            d.flags = CZ_DESC_CHECK_NONCE;
+            d.prev = k ? (int32_t)(i - 1u) : -1;
+            desc[i] = d;
+        }
+        p += h + size;
+        slot += v2_slot(size, amask);
+    }
+}
+
 // ---- one NaCl box per launch (the jnacl crypto_box_afternm / open_afternm drop-ins) ----------
 // One call used to be a chain of copies and launches (subkey, segments, combine, wipe): ~50 us at
 // 4 KiB against ~11 us for a bare launch + sync (tools/diag/latency_ub.hip).  This kernel does the
@@ -4601,6 +4799,27 @@ hipError_t czk_v2_copy(const cz_v2_item *items, uint32_t count, const void *src,
     const uint32_t per_block = BLOCK / 64;
     hipLaunchKernelGGL(k_v2_copy, dim3((count + per_block - 1) / per_block), dim3(BLOCK), 0, s, items, count,
                        (const uint8_t *)src, (uint8_t *)dst);
+    return hipGetLastError();
+}
+
+hipError_t czk_v2_scan(const cz_v2_stream *streams, uint32_t count, const void *wire, int64_t maxmsgsize,
+                       uint32_t slot_align, cz_v2_stream_result *results, cz_v2_totals *totals, hipStream_t s)
+{
+    if (count)
+        hipLaunchKernelGGL(k_v2_scan, dim3((count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, streams, count,
+                           (const uint8_t *)wire, (long long)maxmsgsize, slot_align, results);
+    // (no streams: the placement alone writes the zero totals)
+    hipLaunchKernelGGL(k_v2_place, dim3(1), dim3(BLOCK), 0, s, results, count, totals);
+    return hipGetLastError();
+}
+
+hipError_t czk_v2_emit(const cz_v2_stream *streams, const cz_v2_stream_result *results, uint32_t count,
+                       const void *wire, uint32_t slot_align, cz_v2_frame *frames, cz_frame_desc *desc, hipStream_t s)
+{
+    if (count == 0 || (!frames && !desc))
+        return hipSuccess;
+    hipLaunchKernelGGL(k_v2_emit, dim3((count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, streams, results, count,
+                       (const uint8_t *)wire, slot_align, frames, desc);
     return hipGetLastError();
 }
 

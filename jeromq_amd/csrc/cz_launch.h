@@ -58,6 +58,12 @@ hipError_t czk_open_segments(const cz_frame_desc *desc, const cz_segment *segs, 
                              uint32_t ncomb, const void *in, void *out, const void *subkeys, void *work,
                              uint16_t *status, uint64_t *nonces, hipStream_t s);
 hipError_t czk_v2_copy(const cz_v2_item *items, uint32_t count, const void *src, void *dst, hipStream_t s);
+// device V2 scan: one lane per stream walks its headers (k_v2_scan), one workgroup places the streams
+// (k_v2_place: first / slot_off, the totals record); then the same walk writes frames and / or descriptors
+hipError_t czk_v2_scan(const cz_v2_stream *streams, uint32_t count, const void *wire, int64_t maxmsgsize,
+                       uint32_t slot_align, cz_v2_stream_result *results, cz_v2_totals *totals, hipStream_t s);
+hipError_t czk_v2_emit(const cz_v2_stream *streams, const cz_v2_stream_result *results, uint32_t count,
+                       const void *wire, uint32_t slot_align, cz_v2_frame *frames, cz_frame_desc *desc, hipStream_t s);
 
 // one NaCl box in one launch
 hipError_t czk_nacl_one(void *st, uint32_t len, int open, void *subcache, int miss, uint32_t out_off,

@@ -2,10 +2,11 @@
 //
 // Reference: zmq/io/coder/v2/V2Encoder.java:31-55 (flags byte, 1-byte or BE64 size),
 // V2Decoder.java:37-105 (flagsReady / oneByteSizeReady / eightByteSizeReady), and the size
-// checks of zmq/io/coder/Decoder.java:76-98.  Parsing stays on the host: it is a sequential walk
-// over one header per frame (the bodies are never touched here), while the byte movement
+// checks of zmq/io/coder/Decoder.java:76-98.  The parse of ONE stream is a sequential walk over one
+// header per frame (the bodies are never touched here) and runs on the host, while the byte movement
 // (packing sealed bodies behind their headers, unpacking received bodies into aligned slots)
-// runs on the device in k_v2_copy.
+// runs on the device in k_v2_copy.  MANY streams are as many independent walks: cz_v2_scan /
+// cz_v2_scan_emit / cz_open_streams run them on the device, one lane per stream, with the same rules.
 #include <stdint.h>
 #include <string.h>
 
@@ -73,6 +74,80 @@ int cz_v2_copy(const cz_v2_item *d_items, uint32_t count, const void *d_src, voi
         return fail(CZ_EINVAL, "cz_v2_copy: null pointer");
     hipError_t e = czk_v2_copy(d_items, count, d_src, d_dst, (hipStream_t)stream);
     return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_v2_copy");
+}
+
+static bool bad_slot_align(uint32_t a) { return a == 0 || a > 4096u || (a & (a - 1u)) != 0; }
+
+int cz_v2_scan(const cz_v2_stream *d_streams, uint32_t count, const void *d_wire, int64_t maxmsgsize,
+               uint32_t slot_align, cz_v2_stream_result *d_results, cz_v2_totals *d_totals, void *stream)
+{
+    if (!d_totals || (count && (!d_streams || !d_wire || !d_results)))
+        return fail(CZ_EINVAL, "cz_v2_scan: null pointer");
+    if (bad_slot_align(slot_align))
+        return fail(CZ_EINVAL, "cz_v2_scan: slot_align %u is not a power of two from 1 to 4096", slot_align);
+    hipError_t e = czk_v2_scan(d_streams, count, d_wire, maxmsgsize, slot_align, d_results, d_totals, (hipStream_t)stream);
+    return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_v2_scan");
+}
+
+int cz_v2_scan_emit(const cz_v2_stream *d_streams, const cz_v2_stream_result *d_results, uint32_t count,
+                    const void *d_wire, uint32_t slot_align, cz_v2_frame *d_frames, cz_frame_desc *d_desc, void *stream)
+{
+    if (count && (!d_streams || !d_wire || !d_results))
+        return fail(CZ_EINVAL, "cz_v2_scan_emit: null pointer");
+    if (bad_slot_align(slot_align))
+        return fail(CZ_EINVAL, "cz_v2_scan_emit: slot_align %u is not a power of two from 1 to 4096", slot_align);
+    hipError_t e = czk_v2_emit(d_streams, d_results, count, d_wire, slot_align, d_frames, d_desc, (hipStream_t)stream);
+    return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_v2_scan_emit");
+}
+
+// the calling thread's device totals record of cz_open_streams, per device (never freed: at thread or
+// process exit the runtime may be gone first)
+static thread_local struct {
+    DevBuf buf;
+    int device = -1;
+} t_totals;
+
+int cz_open_streams(const cz_v2_stream *d_streams, uint32_t count, const void *d_wire, int64_t maxmsgsize,
+                    uint32_t slot_align, cz_v2_stream_result *d_results, cz_frame_desc *d_desc, uint64_t desc_cap,
+                    void *d_out, uint64_t out_cap, const void *d_subkeys, uint16_t *d_status, uint64_t *d_nonces,
+                    cz_v2_totals *h_totals, void *stream)
+{
+    if (!h_totals || !d_subkeys || !d_status || (desc_cap && !d_desc) || (out_cap && !d_out) ||
+        (count && (!d_streams || !d_wire || !d_results)))
+        return fail(CZ_EINVAL, "cz_open_streams: null pointer");
+    if (bad_slot_align(slot_align))
+        return fail(CZ_EINVAL, "cz_open_streams: slot_align %u is not a power of two from 1 to 4096", slot_align);
+    *h_totals = {0, 0};
+    if (count == 0)
+        return CZ_OK;
+    hipStream_t s = (hipStream_t)stream;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess)
+        return hip_fail(e, "cz_open_streams");
+    if (dev != t_totals.device) {
+        t_totals.buf = DevBuf{};
+        t_totals.device = -1;
+        if ((e = t_totals.buf.reserve(sizeof(cz_v2_totals))) != hipSuccess)
+            return hip_fail(e, "cz_open_streams: hipMalloc");
+        t_totals.device = dev;
+    }
+    cz_v2_totals *d_totals = (cz_v2_totals *)t_totals.buf.ptr;
+    if ((e = czk_v2_scan(d_streams, count, d_wire, maxmsgsize, slot_align, d_results, d_totals, s)) != hipSuccess ||
+        (e = hipMemcpyAsync(h_totals, d_totals, sizeof *h_totals, hipMemcpyDeviceToHost, s)) != hipSuccess ||
+        (e = hipStreamSynchronize(s)) != hipSuccess)
+        return hip_fail(e, "cz_open_streams: scan");
+    if (h_totals->nframes > 0x7fffffffull)
+        return fail(CZ_EINVAL, "cz_open_streams: %llu frames, more than 2^31 - 1", (unsigned long long)h_totals->nframes);
+    if (h_totals->nframes > desc_cap || h_totals->slot_bytes > out_cap)
+        return fail(CZ_ENOMEM, "cz_open_streams: %llu frames / %llu slot bytes exceed desc_cap %llu / out_cap %llu",
+                    (unsigned long long)h_totals->nframes, (unsigned long long)h_totals->slot_bytes,
+                    (unsigned long long)desc_cap, (unsigned long long)out_cap);
+    if ((e = czk_v2_emit(d_streams, d_results, count, d_wire, slot_align, nullptr, d_desc, s)) != hipSuccess ||
+        (e = czk_open_desc(d_desc, nullptr, (uint32_t)h_totals->nframes, d_wire, d_out, d_subkeys, d_status, d_nonces,
+                           s)) != hipSuccess)
+        return hip_fail(e, "cz_open_streams: open");
+    return CZ_OK;
 }
 
 }  // extern "C"

@@ -220,6 +220,13 @@ class CurveBatchEngine:
         cz_tune("fanin_split") bytes (0: the rule is off)."""
         return int(self._L.cz_engine_fanin_split_frames(self._h))
 
+    @property
+    def scan_frames(self):
+        """Frames of the last flush_in that the scanned path opened: parsed on the device (cz_v2_scan) and
+        opened from the wire bytes where they lie.  The whole flush or nothing: cz_tune("scan_in") = n > 0,
+        at least 64 connections with received bytes, none holding more than n."""
+        return int(self._L.cz_engine_scan_frames(self._h))
+
     def messages_in(self, conn):
         cnt = ctypes.c_uint32()
         _lib.check(self._L.cz_engine_msgs_in(self._h, conn, ctypes.byref(cnt)), "cz_engine_msgs_in")
