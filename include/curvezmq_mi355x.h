@@ -500,6 +500,67 @@ int cz_open_fanin_split(const cz_fanin_run *d_runs, uint32_t nruns, const cz_fan
                         const void *d_in, const cz_fanin_sub *d_subs, const void *d_subkeys, void *d_out,
                         void *d_work, uint16_t *d_status, uint64_t *d_nonces, void *stream);
 
+/* ---- 3h. relay: received bodies re-sealed for another peer in one launch ---------------------
+ * What a broker does with most of its traffic: a frame arrives under connection A's key and leaves
+ * under connection B's key and nonce.  Replaces Proxy.forward (zmq/Proxy.java:140-160: from.recv, then
+ * to.send) -> CurveServerMechanism.decode (CurveServerMechanism.java:165-225) / CurveClientMechanism.decode
+ * (CurveClientMechanism.java:165-224) on one StreamEngine -> encode (:126-163) on another.  With sections
+ * 3 above that is cz_open_batch, which writes the plaintext to device memory, and cz_seal_batch, which
+ * reads it back.  A re-sealed MESSAGE body has exactly the size and layout of the received one
+ * ("\x07MESSAGE" | nonce8 | tag16 | c), and from box byte 32 on c_out = c_in ^ ks_in ^ ks_out: one pass,
+ * one load stream and one store stream, the authenticated plaintext in registers only, and the V2
+ * header in front of the body stays valid (size and MORE are unchanged).
+ *
+ * ACCEPTED FRAME: the output is, byte for byte, what Mechanism.encode produces for the Msg that
+ * Mechanism.decode delivers: the payload unchanged, the flags byte decrypted_flags & (CZ_MSG_MORE |
+ * CZ_MSG_COMMAND) -- the reference keeps only these two bits through a Msg
+ * (CurveServerMechanism.java:207-213 and :132-138) --, the outbound nonce and the tag under the
+ * outbound subkey.  REJECTED FRAME (any status but CZ_STATUS_OK): its `len` / `size` output bytes are
+ * written as zero -- a COMMAND, MALFORMED or SEQUENCE frame is rejected before decryption; a bad tag
+ * is found after the body was emitted and its bytes are overwritten before the kernel ends.  A zero
+ * body cannot parse as MESSAGE: no sealed copy of unauthenticated plaintext is ever left in d_out.
+ *
+ * cz_relay_batch: one lane per frame, no new record types.  d_desc[i] is read exactly as cz_open_batch
+ * reads it (in_off, len = the body size, key_idx = the inbound subkey, counter = the floor,
+ * CZ_DESC_CHECK_NONCE, prev); out_off is where the re-sealed body of the same len bytes goes.  d_to[i]
+ * is the cz_fanout_sub {counter, key_idx} of section 3c: the outbound cnNonce and the outbound subkey
+ * in the same table.  Inbound and outbound key, and inbound and outbound counter, may be equal.
+ * Input and output at any byte alignment, independently of each other.  d_order as in cz_open_batch.
+ * d_status[i] and d_nonces[i] (optional) are exactly cz_open_batch's: the full decrypted flags byte in
+ * bits 8..15 of an OK status, and the inbound wire nonce.  len == 0 writes nothing.
+ * IN PLACE: d_out + out_off == d_in + in_off is legal for a frame with prev < 0 (the lane reads the
+ * header, the tag and each block before it stores over them).  With prev >= 0 an in-place relay is
+ * the caller's error: the floor would be read from a body another lane may already have re-sealed.
+ * Any other overlap of input and output ranges is the caller's error too.
+ * Null pointers (d_order and d_nonces are optional): CZ_EINVAL, checked before the device is touched.
+ * count == 0: CZ_OK, nothing launched.  No device: CZ_EHIP; there is no CPU fallback.  Asynchronous on
+ * `stream`; allocates nothing; can be captured into a graph. */
+int cz_relay_batch(const cz_frame_desc *d_desc, const cz_fanout_sub *d_to, const uint32_t *d_order, uint32_t count,
+                   const void *d_in, void *d_out, const void *d_subkeys, uint16_t *d_status, uint64_t *d_nonces,
+                   void *stream);
+/* One connection's bodies forwarded to one connection, the throughput form (a streamer, one backend):
+ * `count` bodies of `size` bytes at d_in + i * in_stride, re-sealed to d_out + i * out_stride.  Replaces
+ * the same Proxy.forward -> decode -> encode path (Proxy.java:140-160, CurveServerMechanism.java:165-225 /
+ * CurveClientMechanism.java:165-224, :126-163), once per message.
+ * CHAIN: cz_open_uniform's rule -- frame 0 must beat floor0, frame i the wire nonce of frame i - 1,
+ * whether that frame was accepted or not (when check != 0).  d_status[i] as cz_open_uniform.
+ * COUNTERS: frame i is re-sealed with nonce counter0 + i (mod 2^64, as cz_seal_uniform).  A rejected
+ * frame still consumes its counter: the outbound stream then has a gap, which a CURVE receiver
+ * accepts because it asks only for a strictly increasing nonce (CurveClientMechanism.java:186-193).
+ * OUTPUT OWNERSHIP by out_stride alone, the rule of cz_seal_uniform: an owning stride gets zeros past
+ * each body and over a rejected frame's whole slot; any other stride writes only the `size` bytes of
+ * each body, as zeros when the frame is rejected.  size < 33: every frame is COMMAND or MALFORMED and
+ * only zeros are written.
+ * Input and output ranges must not overlap: there is no in-place here (the line stores of a body are
+ * issued by other lanes).  Full waves of bodies of at least 256 bytes with d_in, in_stride, d_out and
+ * out_stride on 16 bytes and out_stride a multiple of 128 below 32 MiB store whole lines; every other
+ * layout (the dense stride 4129, the last partial wave) is stored lane by lane, byte-exact.
+ * Null pointers: CZ_EINVAL before the device is touched; count == 0: CZ_OK; no device: CZ_EHIP, no CPU
+ * fallback; asynchronous on `stream`, allocates nothing, can be captured into a graph. */
+int cz_relay_uniform(uint32_t count, uint32_t size, const void *d_in, uint64_t in_stride, void *d_out,
+                     uint64_t out_stride, const void *d_subkey_in, uint64_t floor0, int check,
+                     const void *d_subkey_out, uint64_t counter0, uint16_t *d_status, void *stream);
+
 /* Synthetic data: fill d_buf with the counter-based SplitMix64 byte stream (seed). */
 int cz_fill(void *d_buf, uint64_t nbytes, uint64_t seed, void *stream);
 /* Measurement: device-to-device copy of nbytes (a multiple of 16) with 16-byte loads and stores,

@@ -417,6 +417,82 @@ def open_batch(desc, count, inp, out, subkeys_t, status, nonces=None, order=None
                                         _ptr(status), _ptr(nonces), _stream(stream)), "cz_open_batch")
 
 
+def _check_relay_bounds(desc_np, to_np, count, in_bytes, out_bytes, nkeys, nstatus, nnonces):
+    """Every frame's body inside `in`, its re-sealed body of the same size inside `out`, both key indices
+    inside the table, and one status (and nonce) entry per frame."""
+    if nstatus < count or (nnonces is not None and nnonces < count):
+        raise ValueError("status / nonces hold fewer than count records")
+    if desc_np is not None:
+        if len(desc_np) < count:
+            raise ValueError("desc_np holds fewer than count descriptors")
+        d = desc_np[:count]
+        ln = d["len"].astype(np.uint64)
+        if count and (np.any(d["in_off"] + ln > np.uint64(in_bytes)) or np.any(d["out_off"] + ln > np.uint64(out_bytes))
+                      or np.any(d["key_idx"] >= nkeys) or np.any(d["prev"] >= count)):
+            raise ValueError("descriptor out of bounds")
+    if to_np is not None:
+        if len(to_np) < count:
+            raise ValueError("to_np holds fewer than count records")
+        if count and np.any(to_np["key_idx"][:count] >= nkeys):
+            raise ValueError("outbound key index out of bounds")
+
+
+def relay_batch(desc, to, count, inp, out, subkeys_t, status, nonces=None, order=None, stream=None, desc_np=None,
+                to_np=None):
+    """Relay `count` received MESSAGE bodies (cz_relay_batch): frame i, read as open_batch reads desc[i],
+    is re-sealed at out[desc[i].out_off] with the same size under subkey to[i].key_idx and nonce
+    to[i].counter (to: a device tensor of 16-byte cz_fanout_sub records, FANOUT_SUB_DTYPE).  status and
+    nonces as open_batch; a rejected frame's output bytes are zeros.  The plaintext never reaches memory.
+    With the host copies desc_np / to_np, bounds and both key indices are checked before the launch."""
+    _need_cuda_u8(inp, "in")
+    _need_cuda_u8(out, "out")
+    _need_cuda_u8(subkeys_t, "subkeys")
+    if desc is None or not desc.is_cuda or to is None or not to.is_cuda or status is None or not status.is_cuda:
+        raise ValueError("desc, to and status must be CUDA (HIP) tensors")
+    if (desc.numel() * desc.element_size() < count * DESC_DTYPE.itemsize
+            or to.numel() * to.element_size() < count * FANOUT_SUB_DTYPE.itemsize
+            or (order is not None and order.numel() < count)):
+        raise ValueError("desc / to / order hold fewer than count records")
+    _check_relay_bounds(desc_np, to_np, count, inp.numel(), out.numel(), subkeys_t.shape[0], status.numel(),
+                        None if nonces is None else nonces.numel())
+    _lib.check(_lib.lib().cz_relay_batch(_ptr(desc), _ptr(to), _ptr(order), count, _ptr(inp), _ptr(out),
+                                         _ptr(subkeys_t), _ptr(status), _ptr(nonces), _stream(stream)),
+               "cz_relay_batch")
+
+
+def _check_relay_uniform_bounds(in_bytes, in_stride, out_bytes, out_stride, count, size, nstatus):
+    """`count` bodies inside `in`, their output range (whole slots where the batch owns them) inside
+    `out`, one status entry per frame."""
+    if not count:
+        return
+    if count > 1 and (in_stride < size or out_stride < size):
+        raise ValueError("stride smaller than a body")
+    owns = (out_stride % 128 == 0 and out_stride < (1 << 25)) or (out_stride % 16 == 0 and out_stride <= 256)
+    last = out_stride if owns and out_stride > size else size
+    if in_bytes < (count - 1) * in_stride + size or out_bytes < (count - 1) * out_stride + last or nstatus < count:
+        raise ValueError("buffer too small for the batch")
+
+
+def relay_uniform(inp, in_stride, out, out_stride, count, size, subkey_in, floor0, subkey_out, counter0, status,
+                  check=True, stream=None):
+    """Relay `count` bodies of `size` bytes of one connection, in order (the chain rule of open_uniform), to
+    one connection: body i is re-sealed at out[i*out_stride] under subkey_out with nonce counter0 + i
+    (cz_relay_uniform).  A rejected frame's bytes are zeros and its counter is skipped.  Output
+    ownership by out_stride as seal_uniform.  Input and output must not overlap."""
+    _need_cuda_u8(inp, "in")
+    _need_cuda_u8(out, "out")
+    _need_cuda_u8(subkey_in, "subkey_in")
+    _need_cuda_u8(subkey_out, "subkey_out")
+    if status is None or not status.is_cuda:
+        raise ValueError("status must be a CUDA (HIP) tensor")
+    if subkey_in.numel() < 32 or subkey_out.numel() < 32:
+        raise ValueError("a subkey is 32 bytes")
+    _check_relay_uniform_bounds(inp.numel(), in_stride, out.numel(), out_stride, count, size, status.numel())
+    _lib.check(_lib.lib().cz_relay_uniform(count, size, _ptr(inp), in_stride, _ptr(out), out_stride, _ptr(subkey_in),
+                                           floor0, 1 if check else 0, _ptr(subkey_out), counter0, _ptr(status),
+                                           _stream(stream)), "cz_relay_uniform")
+
+
 def open_streams(streams, wire, results, desc, out, subkeys_t, status, nonces=None, maxmsgsize=-1, slot_align=128,
                  desc_cap=None, out_cap=None, stream=None):
     """Parse and open many received streams where they lie (cz_open_streams): `streams` a device tensor of

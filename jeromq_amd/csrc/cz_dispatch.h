@@ -82,7 +82,7 @@ struct Knobs {
 };
 
 // ---- what a launcher launches -----------------------------------------------
-enum Family { K_SEAL_UNIFORM, K_SEAL_UNIFORM_INA, K_SEAL_FANOUT, K_OPEN_UNIFORM, K_OPEN_UNIFORM_CARRY, K_SEAL_FANOUT_TILES, K_OPEN_FANIN, K_OPEN_FANIN_TILES };
+enum Family { K_SEAL_UNIFORM, K_SEAL_UNIFORM_INA, K_SEAL_FANOUT, K_OPEN_UNIFORM, K_OPEN_UNIFORM_CARRY, K_SEAL_FANOUT_TILES, K_OPEN_FANIN, K_OPEN_FANIN_TILES, K_RELAY_UNIFORM };
 constexpr int64_t PAD_NONE = -1;
 
 struct Launch {
@@ -103,6 +103,13 @@ struct OpenLaunch {
     Launch head, tail;
     uint32_t P, nwaves;
     uint64_t done;
+};
+
+// czk_relay_uniform: `head` over the first `done` frames and, when done < count, the lane-wise `tail`
+// over the frames behind the last full wave
+struct RelayLaunch {
+    Launch head, tail;
+    uint32_t done;
 };
 
 // The output-ownership rule of a uniform batch and of a fan-out run (header sections 3 and 3c), by
@@ -308,6 +315,26 @@ inline OpenLaunch plan_open_uniform(uint64_t in, uint64_t in_stride, uint64_t ou
     // everything 16-byte aligned: the staged emitters, whole-line input as the seal; else lane-wise
     const int st = size >= 33u ? pick_staging(out_stride, nout, ina == 16 && aligned16(out | out_stride)) : (int)ST_DIRECT;
     return OpenLaunch{launch(K_OPEN_UNIFORM, st, k.pair && st != ST_REGION, 16, count)};
+}
+
+// czk_relay_uniform: `count` MESSAGE bodies of `size` bytes at in + i * in_stride re-sealed to out + i * out_stride.
+// The seal's line emitter takes the full waves when body base, in_stride, output base and out_stride are
+// all on 16 bytes, out_stride is a line multiple below LINES_STRIDE_MAX and the body has two lines; the
+// frames behind the last full wave, and every other layout (the dense stride, short bodies, sizes
+// below a MESSAGE's 33 bytes), go lane-wise.  Both kernels write the zeros of owned slots themselves:
+// no zero-pad launch.  No knob changes this plan.
+inline RelayLaunch plan_relay_uniform(uint64_t in, uint64_t in_stride, uint64_t out, uint64_t out_stride, uint32_t count,
+                                      uint32_t size)
+{
+    auto launch = [&](int st, uint32_t n) {
+        return Launch{K_RELAY_UNIFORM, st, false, 16, MODE_ZMQ, blocks_for(n), staging_lds(st, out_stride, true), PAD_NONE};
+    };
+    const bool lines = aligned16(in | in_stride | out | out_stride) && out_stride % 128 == 0 &&
+                       out_stride < LINES_STRIDE_MAX && size >= LINES_BYTES_MIN;
+    const uint32_t full = count & ~63u;
+    if (lines && full)
+        return RelayLaunch{launch(ST_LINES, full), launch(ST_DIRECT, count - full), full};
+    return RelayLaunch{launch(ST_DIRECT, count), launch(ST_DIRECT, 0), count};
 }
 
 // ---- segment launchers --------------------------------------------------------

@@ -1202,6 +1202,36 @@ int cz_open_uniform(uint32_t count, uint32_t size, const void *d_in, uint64_t in
     return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_open_uniform");
 }
 
+int cz_relay_batch(const cz_frame_desc *d_desc, const cz_fanout_sub *d_to, const uint32_t *d_order, uint32_t count,
+                   const void *d_in, void *d_out, const void *d_subkeys, uint16_t *d_status, uint64_t *d_nonces,
+                   void *stream)
+{
+    if (count == 0)
+        return CZ_OK;
+    if (!d_desc || !d_to || !d_in || !d_out || !d_subkeys || !d_status)
+        return fail(CZ_EINVAL, "cz_relay_batch: null pointer");
+    hipError_t e = czk_relay_desc(d_desc, d_to, d_order, count, d_in, d_out, d_subkeys, d_status, d_nonces,
+                                  (hipStream_t)stream);
+    return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_relay_batch");
+}
+
+int cz_relay_uniform(uint32_t count, uint32_t size, const void *d_in, uint64_t in_stride, void *d_out,
+                     uint64_t out_stride, const void *d_subkey_in, uint64_t floor0, int check,
+                     const void *d_subkey_out, uint64_t counter0, uint16_t *d_status, void *stream)
+{
+    if (count == 0)
+        return CZ_OK;
+    if (!d_in || !d_out || !d_subkey_in || !d_subkey_out || !d_status)
+        return fail(CZ_EINVAL, "cz_relay_uniform: null pointer");
+    if (count > 1 && (in_stride < size || out_stride < size))
+        return fail(CZ_EINVAL, "cz_relay_uniform: stride smaller than the frame");
+    if (!uniform_span(count, in_stride, size, nullptr) || !uniform_span(count, out_stride, size, nullptr))
+        return fail(CZ_EINVAL, "cz_relay_uniform: count x stride overflows the address space");
+    hipError_t e = czk_relay_uniform(d_in, in_stride, d_out, out_stride, count, size, d_subkey_in, floor0, check,
+                                     d_subkey_out, counter0, d_status, (hipStream_t)stream);
+    return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_relay_uniform");
+}
+
 int cz_plan_order(const cz_frame_desc *h_desc, uint32_t count, uint32_t *h_order)
 {
     if (count && (!h_desc || !h_order))

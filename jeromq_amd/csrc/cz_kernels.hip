@@ -4372,6 +4372,9 @@ __global__ __launch_bounds__(BLOCK) void k_copy16(uint4 *__restrict__ dst, const
     }
 }
 
+// CURVE relay (header section 3h): relay_frame, k_relay_desc, k_relay_uniform
+#include "cz_relay_kernels.h"
+
 #endif  // CZ_KPART_HAS(3)
 
 }  // namespace
@@ -4857,6 +4860,51 @@ hipError_t czk_fill(void *buf, uint64_t nbytes, uint64_t seed, hipStream_t s)
     uint64_t chunks = (nbytes + 15) / 16;
     dim3 grid((unsigned)((chunks + BLOCK - 1) / BLOCK));
     hipLaunchKernelGGL(k_fill, grid, dim3(BLOCK), 0, s, (uint8_t *)buf, nbytes, seed);
+    return hipGetLastError();
+}
+
+// CURVE relay (k_relay_desc): one lane per frame, as czk_open_desc
+hipError_t czk_relay_desc(const cz_frame_desc *desc, const cz_fanout_sub *to, const uint32_t *order, uint32_t count,
+                          const void *in, void *out, const void *subkeys, uint16_t *status, uint64_t *nonces,
+                          hipStream_t s)
+{
+    if (count == 0)
+        return hipSuccess;
+    dim3 grid((count + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(k_relay_desc, grid, dim3(BLOCK), 0, s, desc, to, order, count, (const uint8_t *)in,
+                       (uint8_t *)out, (const uint8_t *)subkeys, status, nonces);
+    return hipGetLastError();
+}
+
+// Uniform relay: the plan's head over its first frames and, if it has one, the lane-wise tail over
+// the frames behind the last full wave (floor from the body before, counters counter0 + done ...)
+hipError_t czk_relay_uniform(const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint32_t count,
+                             uint32_t size, const void *subkey_in, uint64_t floor0, int check, const void *subkey_out,
+                             uint64_t counter0, uint16_t *status, hipStream_t s)
+{
+    if (count == 0)
+        return hipSuccess;
+    const RelayLaunch p = plan_relay_uniform((uintptr_t)in, in_stride, (uintptr_t)out, out_stride, count, size);
+    const uint8_t *bin = (const uint8_t *)in;
+    uint8_t *bout = (uint8_t *)out;
+    for (int part = 0; part < 2; part++) {
+        const Launch &l = part ? p.tail : p.head;
+        const uint64_t first = part ? p.done : 0;
+        const uint32_t n = part ? count - p.done : p.done;
+        if (n == 0)
+            break;
+#define CZ_CASE(ST)                                                                                                  \
+    case ST:                                                                                                         \
+        CZ_LAUNCH((k_relay_uniform<ST>), dim3(l.grid), dim3(BLOCK), l.lds, s, bin + first * in_stride, in_stride,    \
+                  bout + first * out_stride, out_stride, n, size, (const uint8_t *)subkey_in, floor0, check,         \
+                  (const uint8_t *)subkey_out, counter0 + first, status + first, part);                              \
+        break;
+        switch (l.st) {
+            CZ_CASE(ST_LINES) CZ_CASE(ST_DIRECT)
+        default: return hipErrorInvalidValue;
+        }
+#undef CZ_CASE
+    }
     return hipGetLastError();
 }
 

@@ -65,6 +65,14 @@ hipError_t czk_v2_scan(const cz_v2_stream *streams, uint32_t count, const void *
 hipError_t czk_v2_emit(const cz_v2_stream *streams, const cz_v2_stream_result *results, uint32_t count,
                        const void *wire, uint32_t slot_align, cz_v2_frame *frames, cz_frame_desc *desc, hipStream_t s);
 
+// CURVE relay: received bodies re-sealed for another peer in one pass (descriptor batch; one connection to one)
+hipError_t czk_relay_desc(const cz_frame_desc *desc, const cz_fanout_sub *to, const uint32_t *order, uint32_t count,
+                          const void *in, void *out, const void *subkeys, uint16_t *status, uint64_t *nonces,
+                          hipStream_t s);
+hipError_t czk_relay_uniform(const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint32_t count,
+                             uint32_t size, const void *subkey_in, uint64_t floor0, int check, const void *subkey_out,
+                             uint64_t counter0, uint16_t *status, hipStream_t s);
+
 // one NaCl box in one launch
 hipError_t czk_nacl_one(void *st, uint32_t len, int open, void *subcache, int miss, uint32_t out_off,
                         const uint8_t k[32], const uint8_t n[24], hipStream_t s);

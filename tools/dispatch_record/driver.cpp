@@ -6,6 +6,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <string>
 #include <vector>
 
 #include "curvezmq_mi355x.h"
@@ -28,6 +29,9 @@ hipError_t czk_seal_segments(const cz_frame_desc *, const cz_segment *, uint32_t
 hipError_t czk_open_segments(const cz_frame_desc *, const cz_segment *, uint32_t, const cz_combine *, uint32_t,
                              const void *, void *, const void *, void *, uint16_t *, uint64_t *, hipStream_t);
 int czk_tune(const char *, int);
+// (weak: a revision of csrc/ from before the relay still links, and records no relay case)
+hipError_t czk_relay_uniform(const void *, uint64_t, void *, uint64_t, uint32_t, uint32_t, const void *, uint64_t, int,
+                             const void *, uint64_t, uint16_t *, hipStream_t) __attribute__((weak));
 }
 
 namespace {
@@ -283,6 +287,35 @@ void segment_cases()
     }
 }
 
+// The relay's grid (`dispatch_record.py --relay`; not part of the default record): base and stride
+// phases of input and output, the line emitter's stride and size limits, counts around a wave, every knob
+void relay(uint64_t ib, uint64_t is, uint64_t ob, uint64_t os, uint32_t n, uint32_t size)
+{
+    layout("relay", ib, is, ob, os, n, size);
+    result(czk_relay_uniform(ptr<void>(IN + ib), is, ptr<void>(OUT + ob), os, n, size, ptr<void>(KEY), 5, 1,
+                             ptr<void>(KEY + 32), 9, ptr<uint16_t>(AUX), nullptr));
+}
+
+void relay_cases()
+{
+    if (!czk_relay_uniform)
+        return;
+    phase_cases(relay, {4224, 4144, 4136, 4129}, {4224, 4144, 4136, 4129}, 4129);
+    phase_cases(relay, {144, 136, 133}, {256, 144, 133}, 133);
+    for (uint32_t size : {0u, 1u, 32u, 33u, 255u, 256u, 257u, 4129u})
+        for (uint64_t os : strides_for(size, false))
+            relay(0, (size + 15u) & ~15ull, 0, os, 1000, size);
+    for (uint32_t n : {1u, 63u, 64u, 65u, 127u, 128u, 129u, 1000u, 1024u, 1025u, 1u << 20})
+        for (uint64_t os : {4224u, 4129u})
+            relay(0, 4144, 0, os, n, 4129);
+    for (const Knob &k : KNOBS) {
+        WithKnob w(k);
+        relay(0, 4144, 0, 4224, 1025, 4129);
+        relay(1, 4129, 0, 4224, 1025, 4129);
+        relay(0, 4144, 0, 4129, 1025, 4129);
+    }
+}
+
 // czk_tune: the old value it returns, what a value is clamped to, an unknown key
 void tune_cases()
 {
@@ -296,8 +329,12 @@ void tune_cases()
 
 }  // namespace
 
-int main()
+int main(int argc, char **argv)
 {
+    if (argc > 1 && std::string(argv[1]) == "relay") {
+        relay_cases();
+        return 0;
+    }
     seal_cases();
     open_cases();
     box_cases();

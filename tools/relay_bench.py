@@ -1,0 +1,272 @@
+#!/usr/bin/env python3
+"""CURVE relay (cz_relay_uniform / cz_relay_batch, header section 3h) against the two calls it replaces.
+
+Every leg interleaves the relay with the two-call path in one process: shapes warmed, --reps (at least 10)
+alternations, the median and the spread of each side reported, and the outputs of both sides compared at the
+timed size (byte-equal bodies, every frame accepted).  The yardstick is the two-call path on the same build.
+
+Device legs (HIP events around one call of each side):
+  uniform  cz_relay_uniform  against  cz_open_uniform into 4224- / 144-byte plaintext slots, then cz_seal_uniform
+           2^20 x 4129-byte bodies in 4224-byte slots; 2^20 x 133-byte bodies in 144-byte slots;
+           2^20 x 4129-byte bodies at the dense stride 4129
+  batch    cz_relay_batch    against  cz_open_batch then cz_seal_batch, the same descriptors
+           2^16 frames of 1 KiB payload under 1024 key pairs
+Host-staged leg (pinned torch tensors, one stream, a host clock ending in a synchronise), 2^16 x 4 KiB:
+  relay     H2D bodies -> cz_relay_uniform -> D2H bodies
+  two-call  H2D bodies -> open -> D2H payloads -> H2D payloads -> seal -> D2H bodies
+
+Writes profiles/relay/relay.json and prints it.  --log2 / --batch-log2 / --host-log2 shrink the shapes for a
+rehearsal; the committed file is measured at the defaults.  --pmc: one call of each side at the first uniform
+shape, for a counter run:
+  rocprofv3 --pmc SQ_INSTS_VALU --output-format csv -d DIR -o run -- python3 tools/relay_bench.py --pmc"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+KERNELS = ["k_relay_uniform<1>", "k_relay_uniform<0>", "k_relay_desc"]
+# (name, body size, in_stride, out_stride, plaintext stride)
+UNIFORM_SHAPES = (("4k_slots", 4129, 4224, 4224, 4224), ("100b_slots", 133, 144, 144, 144),
+                  ("4k_dense", 4129, 4129, 4129, 4224))
+
+
+def round_up(v, a):
+    return (v + a - 1) // a * a
+
+
+def event_ms(torch, fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def wall_ms(torch, fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def alternate(torch, clock, legs, reps):
+    """warm every leg once, then `reps` alternations; per leg the median, the extremes and the spread"""
+    for fn in legs.values():
+        clock(torch, fn)
+    times = {k: [] for k in legs}
+    for _ in range(reps):
+        for k, fn in legs.items():
+            times[k].append(clock(torch, fn))
+    row = {}
+    for k, t in times.items():
+        med = statistics.median(t)
+        row[k + "_ms"] = round(med, 5)
+        row[k + "_min_ms"], row[k + "_max_ms"] = round(min(t), 5), round(max(t), 5)
+        row[k + "_spread"] = round((max(t) - min(t)) / med, 4)
+        row[k + "_all_ms"] = [round(v, 5) for v in t]
+    return row
+
+
+def finish(row, body_bytes):
+    row["relay_over_two_call"] = round(row["relay_ms"] / row["two_call_ms"], 4)
+    row["relay_gib_s"] = round(body_bytes / 2**30 / (row["relay_ms"] * 1e-3), 1)
+    row["two_call_gib_s"] = round(body_bytes / 2**30 / (row["two_call_ms"] * 1e-3), 1)
+    return row
+
+
+def make_bodies(torch, batch, dev, count, size, stride, key, counter0, scratch_stride):
+    """`count` MESSAGE bodies of `size` bytes at `stride`, sealed on the device from synthetic payloads"""
+    length = size - 33
+    plain = torch.empty(count * scratch_stride + 64, dtype=torch.uint8, device=dev)
+    batch.fill(plain, 11)
+    bodies = torch.zeros(count * stride + 64, dtype=torch.uint8, device=dev)
+    batch.seal_uniform(plain, scratch_stride, bodies, stride, count, length, key, counter0)
+    return bodies, plain
+
+
+def uniform_leg(args, torch, dev, batch, name, size, ist, ost, pst, once=False):
+    count = 1 << args.log2
+    keys = torch.empty(64, dtype=torch.uint8, device=dev)
+    batch.fill(keys, 5)
+    k_in, k_out = keys[:32], keys[32:]
+    floor0, counter0 = (1 << 33) + 5, (7 << 32) - 1000
+    bodies, plain = make_bodies(torch, batch, dev, count, size, ist, k_in, floor0 + 1, pst)
+    out_r = torch.zeros(count * ost + 64, dtype=torch.uint8, device=dev)
+    out_t = torch.zeros(count * ost + 64, dtype=torch.uint8, device=dev)
+    st_r = torch.full((count,), -1, dtype=torch.int16, device=dev)
+    st_t = torch.full((count,), -1, dtype=torch.int16, device=dev)
+    n_in, n_out = (count - 1) * ist + size, count * ost if ost % 16 == 0 else (count - 1) * ost + size
+
+    def relay():
+        batch.relay_uniform(bodies[:n_in], ist, out_r[:n_out], ost, count, size, k_in, floor0, k_out, counter0, st_r)
+
+    def two_call():
+        batch.open_uniform(bodies[:n_in], ist, plain, pst, count, size, k_in, floor0, st_t)
+        batch.seal_uniform(plain, pst, out_t[:n_out], ost, count, size - 33, k_out, counter0)
+
+    relay()
+    two_call()
+    torch.cuda.synchronize()
+    assert int((st_r != 0).sum()) == 0 and int((st_t != 0).sum()) == 0, "a body was rejected"
+    assert torch.equal(out_r, out_t), "cz_relay_uniform and open + seal disagree"
+    if once:
+        return None
+    row = {"leg": name, "count": count, "size": size, "in_stride": ist, "out_stride": ost, "plain_stride": pst}
+    row.update(alternate(torch, event_ms, {"relay": relay, "two_call": two_call}, args.reps))
+    return finish(row, count * size)
+
+
+def batch_leg(args, torch, dev, batch):
+    count, pairs, length = 1 << args.batch_log2, 1024, 1024
+    size, slot, pslot = length + 33, round_up(length + 33, 16), round_up(length, 16)
+    keys = torch.empty(2 * pairs * 32, dtype=torch.uint8, device=dev)
+    batch.fill(keys, 7)
+    keys = keys.view(2 * pairs, 32)
+    idx = np.arange(count, dtype=np.uint64)
+    k_in = (2 * (idx % pairs)).astype(np.uint32)
+    k_out = (2 * ((idx * 7 + 1) % pairs) + 1).astype(np.uint32)
+    plain = torch.empty(count * pslot + 64, dtype=torch.uint8, device=dev)
+    batch.fill(plain, 13)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)  # noqa: E731
+    # the received bodies: sealed under the inbound keys
+    sd = np.zeros(count, dtype=batch.DESC_DTYPE)
+    sd["in_off"], sd["out_off"], sd["len"], sd["key_idx"] = idx * pslot, idx * slot, length, k_in
+    sd["counter"], sd["prev"] = idx + 100, -1
+    bodies = torch.zeros(count * slot + 64, dtype=torch.uint8, device=dev)
+    batch.seal_batch(up(sd), count, plain, bodies, keys, desc_np=sd)
+    # relay / open descriptors (the same records), the outbound records, and the second call's seal descriptors
+    od = np.zeros(count, dtype=batch.DESC_DTYPE)
+    od["in_off"], od["len"], od["key_idx"], od["counter"] = idx * slot, size, k_in, idx + 99
+    od["flags"], od["prev"] = 0x100, -1
+    rd = od.copy()
+    rd["out_off"] = idx * slot
+    od["out_off"] = idx * pslot
+    to = np.zeros(count, dtype=batch.FANOUT_SUB_DTYPE)
+    to["counter"], to["key_idx"] = idx + (1 << 40), k_out
+    td = sd.copy()
+    td["key_idx"], td["counter"] = k_out, to["counter"]
+    d_rd, d_od, d_to, d_td = up(rd), up(od), up(to), up(td)
+    out_r = torch.zeros(count * slot + 64, dtype=torch.uint8, device=dev)
+    out_t = torch.zeros(count * slot + 64, dtype=torch.uint8, device=dev)
+    st_r = torch.full((count,), -1, dtype=torch.int16, device=dev)
+    st_t = torch.full((count,), -1, dtype=torch.int16, device=dev)
+
+    def relay():
+        batch.relay_batch(d_rd, d_to, count, bodies, out_r, keys, st_r)
+
+    def two_call():
+        batch.open_batch(d_od, count, bodies, plain, keys, st_t)
+        batch.seal_batch(d_td, count, plain, out_t, keys)
+
+    batch.relay_batch(d_rd, d_to, count, bodies, out_r, keys, st_r, desc_np=rd, to_np=to)      # bounds, once
+    two_call()
+    torch.cuda.synchronize()
+    assert int((st_r != 0).sum()) == 0 and int((st_t != 0).sum()) == 0, "a body was rejected"
+    assert torch.equal(out_r, out_t), "cz_relay_batch and open_batch + seal_batch disagree"
+    row = {"leg": "batch_1k_1024_pairs", "count": count, "size": size, "key_pairs": pairs, "slot": slot}
+    row.update(alternate(torch, event_ms, {"relay": relay, "two_call": two_call}, args.reps))
+    return finish(row, count * size)
+
+
+def host_leg(args, torch, dev, batch):
+    count, size, ist, pst = 1 << args.host_log2, 4129, 4224, 4096
+    keys = torch.empty(64, dtype=torch.uint8, device=dev)
+    batch.fill(keys, 9)
+    k_in, k_out = keys[:32], keys[32:]
+    floor0, counter0 = 77, 1 << 35
+    d_bodies, _ = make_bodies(torch, batch, dev, count, size, ist, k_in, floor0 + 1, ist)
+    nb, npl = count * ist, count * pst
+    h_in = torch.empty(nb, dtype=torch.uint8).pin_memory()
+    h_in.copy_(d_bodies[:nb])
+    h_out_r, h_out_t = torch.zeros(nb, dtype=torch.uint8).pin_memory(), torch.zeros(nb, dtype=torch.uint8).pin_memory()
+    h_plain = torch.zeros(npl, dtype=torch.uint8).pin_memory()
+    d_in = torch.zeros(nb, dtype=torch.uint8, device=dev)
+    d_out = torch.zeros(nb, dtype=torch.uint8, device=dev)
+    d_plain = torch.zeros(npl, dtype=torch.uint8, device=dev)
+    st_r = torch.full((count,), -1, dtype=torch.int16, device=dev)
+    st_t = torch.full((count,), -1, dtype=torch.int16, device=dev)
+
+    def relay():
+        d_in.copy_(h_in, non_blocking=True)
+        batch.relay_uniform(d_in, ist, d_out, ist, count, size, k_in, floor0, k_out, counter0, st_r)
+        h_out_r.copy_(d_out, non_blocking=True)
+
+    def two_call():
+        d_in.copy_(h_in, non_blocking=True)
+        batch.open_uniform(d_in, ist, d_plain, pst, count, size, k_in, floor0, st_t)
+        h_plain.copy_(d_plain, non_blocking=True)
+        d_plain.copy_(h_plain, non_blocking=True)
+        batch.seal_uniform(d_plain, pst, d_out, ist, count, size - 33, k_out, counter0)
+        h_out_t.copy_(d_out, non_blocking=True)
+
+    relay()
+    two_call()
+    torch.cuda.synchronize()
+    assert int((st_r != 0).sum()) == 0 and int((st_t != 0).sum()) == 0, "a body was rejected"
+    assert torch.equal(h_out_r, h_out_t), "the host-staged relay and open + seal disagree"
+    row = {"leg": "host_staged_4k", "count": count, "size": size, "stride": ist, "plain_stride": pst,
+           "relay_pcie_bytes": 2 * nb, "two_call_pcie_bytes": 2 * nb + 2 * npl}
+    row.update(alternate(torch, wall_ms, {"relay": relay, "two_call": two_call}, args.reps))
+    return finish(row, count * size)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--reps", type=int, default=12, help="alternations per leg (at least 10)")
+    ap.add_argument("--log2", type=int, default=20, help="uniform legs: log2 of the frame count")
+    ap.add_argument("--batch-log2", type=int, default=16)
+    ap.add_argument("--host-log2", type=int, default=16)
+    ap.add_argument("--pmc", action="store_true",
+                    help="one call of each side at the first uniform shape and nothing else: the run to put under "
+                         "rocprofv3 --pmc SQ_INSTS_VALU (counters in a run of their own, no tracing)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "relay", "relay.json"))
+    args = ap.parse_args()
+    if args.reps < 10:
+        ap.error("--reps: at least 10 alternations")
+    import torch
+
+    from jeromq_amd import _lib, batch, build
+    if not torch.cuda.is_available():
+        raise SystemExit("relay_bench needs a GPU")
+    dev = torch.device("cuda:0")
+    if args.pmc:
+        uniform_leg(args, torch, dev, batch, *UNIFORM_SHAPES[0], once=True)
+        return
+    out = {"device": torch.cuda.get_device_name(0), "library": _lib.lib().cz_version().decode(),
+           "relay_kernels_sha256": build.kernel_code_sha256(_lib.LIB_PATH, KERNELS), "reps": args.reps,
+           "clock_device": "hipEvent (torch.cuda.Event) around one call of each side, median of the alternations",
+           "clock_host": "time.perf_counter around the copies and calls, ending in a synchronise, median",
+           "spread": "(max - min) / median of a side's alternations", "legs": []}
+
+    def write():
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+    for shape in UNIFORM_SHAPES:
+        out["legs"].append(uniform_leg(args, torch, dev, batch, *shape))
+        torch.cuda.empty_cache()
+        write()
+    out["legs"].append(batch_leg(args, torch, dev, batch))
+    write()
+    out["legs"].append(host_leg(args, torch, dev, batch))
+    write()
+    for r in out["legs"]:
+        print(f"{r['leg']}: relay {r['relay_ms']} ms, two calls {r['two_call_ms']} ms, ratio {r['relay_over_two_call']}",
+              file=sys.stderr)
+    print(json.dumps({k: v for k, v in out.items() if k != "legs"} |
+                     {"legs": [{k: v for k, v in r.items() if not k.endswith("_all_ms")} for r in out["legs"]]}))
+
+
+if __name__ == "__main__":
+    main()
