@@ -561,6 +561,45 @@ int cz_relay_uniform(uint32_t count, uint32_t size, const void *d_in, uint64_t i
                      uint64_t out_stride, const void *d_subkey_in, uint64_t floor0, int check,
                      const void *d_subkey_out, uint64_t counter0, uint16_t *d_status, void *stream);
 
+/* ---- 3i. segmented relay: long received bodies re-sealed across lanes ------------------------
+ * cz_relay_batch keeps a whole frame on one lane: a 64 KiB body is 1025 blocks of double work (two
+ * keystreams, two Poly1305 chains) and a ragged batch waits for its longest frame.  This call is the
+ * relay of section 3h on the segment plan of section 3b: one lane per segment, then one combine lane
+ * per split frame.  It replaces the same reference path, Proxy.forward (zmq/Proxy.java:140-160) ->
+ * Mechanism.decode (CurveServerMechanism.java:165-225 / CurveClientMechanism.java:165-224) ->
+ * Mechanism.encode (:126-163), once per message.
+ *
+ * d_desc[i] and d_to[i] are read exactly as cz_relay_batch reads them (len = the body size, out_off =
+ * where the re-sealed body of the same size goes, prev chains allowed).  THE PLAN is the one
+ * cz_plan_segments(h_desc, count, open = 1, seg_blocks, ...) makes for those descriptors -- the plan a
+ * cz_open_segments of them would take; there is no planner and no record type of its own.  A caller may
+ * build its own plan under section 3b's rule: the segments of a split frame cover box blocks [0, nblk)
+ * contiguously, one or more blocks each, with consecutive part indices from the frame's part0, in any
+ * order in the list.  The open's "block 2 or later" rule is NOT needed here (block q in gives block q
+ * out: a segment's output is its own blocks' bytes); plans that obey it work as well.
+ * WORKSPACE: d_work holds 128 bytes per part, two planes of npart 64-byte records: the inbound Poly1305
+ * partial of part p is record p (cz_open_segments' record, with the flags byte and the early status
+ * from the segment holding block 0), the outbound partial is record npart + p.  d_comb and d_work are
+ * needed only when ncomb != 0.
+ * OUTPUT, byte for byte what cz_relay_batch writes for the same d_desc and d_to: the bodies,
+ * d_status[i] and d_nonces[i] (optional).  Every rejected frame's len output bytes are written as zero;
+ * nothing outside the bodies, and no status or nonce entry of another frame, is touched.  A frame
+ * rejected before decryption (COMMAND, MALFORMED, SEQUENCE): each of its segments zeroes its own byte
+ * range, the segment holding block 0 writes the status and the nonce.  A bad tag on a split frame is
+ * found by the combine lane, which zeroes the whole body and writes CZ_STATUS_CRYPTO: no sealed copy of
+ * unauthenticated plaintext is left in d_out once the call's last kernel has finished.
+ * NO IN PLACE: input and output ranges must not overlap (later segments re-read the header nonce, and
+ * the combine re-reads the inbound tag, after the first segment may already have stored).
+ * Full waves of segments with one block count, bodies and outputs on 16 bytes and no rejected frame
+ * store whole lines; every other wave stores lane by lane, byte-exact at any alignment of either side.
+ * Null pointers (d_nonces is optional; d_comb and d_work only with ncomb != 0): CZ_EINVAL before the
+ * device is touched.  nseg == 0: CZ_OK, nothing launched.  No device: CZ_EHIP; there is no CPU
+ * fallback.  Asynchronous on `stream`, allocates nothing, never synchronises, can be captured into a
+ * graph; at most two launches (segments, then combine). */
+int cz_relay_segments(const cz_frame_desc *d_desc, const cz_fanout_sub *d_to, const cz_segment *d_seg, uint32_t nseg,
+                      const cz_combine *d_comb, uint32_t ncomb, uint32_t npart, const void *d_in, void *d_out,
+                      const void *d_subkeys, void *d_work, uint16_t *d_status, uint64_t *d_nonces, void *stream);
+
 /* Synthetic data: fill d_buf with the counter-based SplitMix64 byte stream (seed). */
 int cz_fill(void *d_buf, uint64_t nbytes, uint64_t seed, void *stream);
 /* Measurement: device-to-device copy of nbytes (a multiple of 16) with 16-byte loads and stores,

@@ -187,6 +187,7 @@ SIGNATURES = {
                                  _VP]),
     "cz_relay_batch": (_I, [_VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "cz_relay_uniform": (_I, [_U32, _U32, _VP, _U64, _VP, _U64, _VP, _U64, _I, _VP, _U64, _VP, _VP]),
+    "cz_relay_segments": (_I, [_VP, _VP, _VP, _U32, _VP, _U32, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "cz_plan_order": (_I, [_VP, _U32, _VP]),
     "cz_plan_segments": (_I, [_VP, _U32, _I, _U32, _VP, _U32, ctypes.POINTER(_U32), _VP, _U32,
                               ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),

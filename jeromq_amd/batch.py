@@ -546,7 +546,8 @@ SEG_BLOCKS = 128  # 8 KiB of box per lane (Zipf sweep: 64 -> 1664, 128 -> 1687-1
 class SegmentPlan:
     """Host plan for a ragged batch: frames longer than 1.5 x seg_blocks are split
     into seg_blocks-block segments (cz_plan_segments).  `to(device)` uploads the
-    segment and combine lists and allocates the partial-record workspace."""
+    segment and combine lists and allocates the partial-record workspace (records=2: the two
+    planes of 64-byte records per part that relay_segments needs)."""
 
     def __init__(self, desc_np, open_=False, seg_blocks=SEG_BLOCKS):
         d = np.ascontiguousarray(desc_np)
@@ -566,11 +567,13 @@ class SegmentPlan:
         self.combines = self.combines[:self.ncomb]
         self.d_seg = self.d_comb = self.d_work = None
 
-    def to(self, device):
+    def to(self, device, records=1):
         import torch
+        if records not in (1, 2):
+            raise ValueError("records: 1 (seal / open) or 2 (relay)")
         self.d_seg = torch.from_numpy(self.segments.view(np.uint8).copy()).to(device)
         self.d_comb = torch.from_numpy(self.combines.view(np.uint8).copy()).to(device)
-        self.d_work = torch.empty(max(self.npart, 1) * 64, dtype=torch.uint8, device=device)
+        self.d_work = torch.empty(max(self.npart, 1) * 64 * records, dtype=torch.uint8, device=device)
         return self
 
 
@@ -594,3 +597,29 @@ def open_segments(desc, plan, inp, out, subkeys_t, status, nonces=None, stream=N
     _lib.check(_lib.lib().cz_open_segments(_ptr(desc), _ptr(plan.d_seg), plan.nseg, _ptr(plan.d_comb), plan.ncomb,
                                            _ptr(inp), _ptr(out), _ptr(subkeys_t), _ptr(plan.d_work), _ptr(status),
                                            _ptr(nonces), _stream(stream)), "cz_open_segments")
+
+
+def relay_segments(desc, to, plan, inp, out, subkeys_t, status, nonces=None, stream=None, desc_np=None, to_np=None):
+    """Ragged relay with long bodies split across lanes (cz_relay_segments; same output, status and nonces
+    as relay_batch).  plan: SegmentPlan(desc_np, open_=True, ...).to(device, records=2) -- the plan an
+    open_segments of the same descriptors takes, with 128 bytes of workspace per part.  Input and output
+    must not overlap.  With the host copies desc_np / to_np, bounds and both key indices are checked
+    before the launch."""
+    _need_cuda_u8(inp, "in")
+    _need_cuda_u8(out, "out")
+    _need_cuda_u8(subkeys_t, "subkeys")
+    if desc is None or not desc.is_cuda or to is None or not to.is_cuda or status is None or not status.is_cuda:
+        raise ValueError("desc, to and status must be CUDA (HIP) tensors")
+    count = desc.numel() * desc.element_size() // DESC_DTYPE.itemsize
+    if to.numel() * to.element_size() < count * FANOUT_SUB_DTYPE.itemsize:
+        raise ValueError("to holds fewer records than desc")
+    if plan.d_seg is None or plan.d_work is None or plan.d_work.numel() < 128 * plan.npart:
+        raise ValueError("plan.d_work holds fewer than 128 bytes per part: SegmentPlan.to(device, records=2)")
+    if plan.nseg and (int(plan.segments["frame"].max()) >= count):
+        raise ValueError("plan names a frame past desc")
+    _check_relay_bounds(desc_np, to_np, count, inp.numel(), out.numel(), subkeys_t.shape[0], status.numel(),
+                        None if nonces is None else nonces.numel())
+    _lib.check(_lib.lib().cz_relay_segments(_ptr(desc), _ptr(to), _ptr(plan.d_seg), plan.nseg, _ptr(plan.d_comb),
+                                            plan.ncomb, plan.npart, _ptr(inp), _ptr(out), _ptr(subkeys_t),
+                                            _ptr(plan.d_work), _ptr(status), _ptr(nonces), _stream(stream)),
+               "cz_relay_segments")

@@ -358,5 +358,12 @@ inline int open_segments_mode(const Knobs &k)
     return (k.seglines ? SEGMODE_LINES : 0) | (k.pair ? SEGMODE_PAIR : 0) | (k.shift16 ? SEGMODE_SHIFT16 : 0) |
            (k.open_ina ? SEGMODE_ANYIN : 0);
 }
+// czk_relay_segments: line-staged stores for the full waves of equal-length aligned segments
+// (seglines), EmitShiftLines for those off the 128-byte lines (shift16); the rows' LDS only with lines
+inline int relay_segments_mode(const Knobs &k)
+{
+    return (k.seglines ? SEGMODE_LINES : 0) | (k.shift16 ? SEGMODE_SHIFT16 : 0);
+}
+inline uint32_t relay_segments_lds(const Knobs &k) { return k.seglines ? WAVES * SHIFT_LDS_BYTES : 0u; }
 
 }  // namespace czd

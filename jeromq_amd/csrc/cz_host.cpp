@@ -1232,6 +1232,21 @@ int cz_relay_uniform(uint32_t count, uint32_t size, const void *d_in, uint64_t i
     return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_relay_uniform");
 }
 
+int cz_relay_segments(const cz_frame_desc *d_desc, const cz_fanout_sub *d_to, const cz_segment *d_seg, uint32_t nseg,
+                      const cz_combine *d_comb, uint32_t ncomb, uint32_t npart, const void *d_in, void *d_out,
+                      const void *d_subkeys, void *d_work, uint16_t *d_status, uint64_t *d_nonces, void *stream)
+{
+    if (nseg == 0)
+        return CZ_OK;
+    if (!d_desc || !d_to || !d_seg || !d_in || !d_out || !d_subkeys || !d_status)
+        return fail(CZ_EINVAL, "cz_relay_segments: null pointer");
+    if (ncomb && (!d_comb || !d_work))
+        return fail(CZ_EINVAL, "cz_relay_segments: null combine list / workspace");
+    hipError_t e = czk_relay_segments(d_desc, d_to, d_seg, nseg, d_comb, ncomb, npart, d_in, d_out, d_subkeys, d_work,
+                                      d_status, d_nonces, (hipStream_t)stream);
+    return e == hipSuccess ? CZ_OK : hip_fail(e, "cz_relay_segments");
+}
+
 int cz_plan_order(const cz_frame_desc *h_desc, uint32_t count, uint32_t *h_order)
 {
     if (count && (!h_desc || !h_order))

@@ -4372,7 +4372,8 @@ __global__ __launch_bounds__(BLOCK) void k_copy16(uint4 *__restrict__ dst, const
     }
 }
 
-// CURVE relay (header section 3h): relay_frame, k_relay_desc, k_relay_uniform
+// CURVE relay (header sections 3h, 3i): relay_frame, k_relay_desc, k_relay_uniform; relay_segment,
+// k_relay_segments, k_relay_combine
 #include "cz_relay_kernels.h"
 
 #endif  // CZ_KPART_HAS(3)
@@ -4905,6 +4906,22 @@ hipError_t czk_relay_uniform(const void *in, uint64_t in_stride, void *out, uint
         }
 #undef CZ_CASE
     }
+    return hipGetLastError();
+}
+
+// Segmented relay: the segments, then the combine over the split frames -- at most two launches
+hipError_t czk_relay_segments(const cz_frame_desc *desc, const cz_fanout_sub *to, const cz_segment *segs, uint32_t nseg,
+                              const cz_combine *comb, uint32_t ncomb, uint32_t npart, const void *in, void *out,
+                              const void *subkeys, void *work, uint16_t *status, uint64_t *nonces, hipStream_t s)
+{
+    if (nseg == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(k_relay_segments, dim3((nseg + BLOCK - 1) / BLOCK), dim3(BLOCK), relay_segments_lds(g_knobs), s,
+                       desc, to, segs, nseg, (const uint8_t *)in, (uint8_t *)out, (const uint8_t *)subkeys,
+                       (u32 *)work, npart, status, nonces, relay_segments_mode(g_knobs));
+    if (ncomb)
+        hipLaunchKernelGGL(k_relay_combine, dim3((ncomb + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, desc, comb, ncomb,
+                           (const uint8_t *)in, (uint8_t *)out, (const u32 *)work, npart, status);
     return hipGetLastError();
 }
 

@@ -72,6 +72,10 @@ hipError_t czk_relay_desc(const cz_frame_desc *desc, const cz_fanout_sub *to, co
 hipError_t czk_relay_uniform(const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint32_t count,
                              uint32_t size, const void *subkey_in, uint64_t floor0, int check, const void *subkey_out,
                              uint64_t counter0, uint16_t *status, hipStream_t s);
+// segmented relay: one lane per segment (two planes of npart 64-byte records in `work`), then the combine
+hipError_t czk_relay_segments(const cz_frame_desc *desc, const cz_fanout_sub *to, const cz_segment *segs, uint32_t nseg,
+                              const cz_combine *comb, uint32_t ncomb, uint32_t npart, const void *in, void *out,
+                              const void *subkeys, void *work, uint16_t *status, uint64_t *nonces, hipStream_t s);
 
 // one NaCl box in one launch
 hipError_t czk_nacl_one(void *st, uint32_t len, int open, void *subcache, int miss, uint32_t out_off,

@@ -30,10 +30,25 @@
 // INA: the input's alignment class, as open_frame (16: AL as given; 8 / 1 with AL: dword-aligned loads).
 // The kernels below instantiate 16 only: 8 / 1 are the loads of a line-staged dense relay, which is open
 // (DESIGN.md section 8).
-template <bool AL, class EM, int INA = 16>
+//
+// SEG (relay_segment): the same block loop over box blocks [sg->b0, min(sg->b1, nblk)) of a body whose
+// header passed open_header (nonce words sg->n0, sg->n1; check_floor, floor and nonce_out are not
+// used).  Output chunk q is box block b0 + q at the emitter's base (out body + 64 * b0), the seal
+// segment's geometry.  Both Poly1305 states are keyed from keystream block 0 of their own side,
+// recomputed per segment as open_segment and seal_segment do.  sg->rec_in == nullptr: the whole frame,
+// finished as above (CZ_STATUS_OK or CZ_STATUS_CRYPTO).  Otherwise the inbound partial goes to rec_in
+// (open_segment's record: h, the Poly block count, and from the block-0 segment the flags byte in [6]
+// and r, pad in [8..15]; [7] is the kernel's), the outbound one to rec_out (seal_segment's record), the
+// tag slot is left to the combine, and the return is CZ_STATUS_OK.  The emit site is one for every
+// lane: a cooperative emitter's wave may hold block-0 segments and later ones side by side.
+struct RelaySeg {
+    u32 n0, n1, b0, b1;
+    u32 *rec_in, *rec_out;
+};
+template <bool AL, class EM, int INA = 16, bool SEG = false>
 __device__ __forceinline__ u32 relay_frame(const uint8_t *in, u32 size, const u32 kin[8], bool check_floor,
                                            long long floor, const u32 kout[8], u64 counter_out, u32 *flags_out,
-                                           u64 *nonce_out, EM &em)
+                                           u64 *nonce_out, EM &em, const RelaySeg *sg = nullptr)
 {
     static_assert(INA == 16 || (AL && (INA == 8 || INA == 1)), "INA 8/1 take the AL code paths");
     const u32 ina = INA == 1 ? (u32)(uintptr_t)in & 3u : 0u;
@@ -60,13 +75,13 @@ __device__ __forceinline__ u32 relay_frame(const uint8_t *in, u32 size, const u3
     constexpr bool COOP = EM::cooperative;
     // header, size and floor: open_frame's checks (Msgs.startsWith never reaches byte 7)
     u32 early = CZ_STATUS_OK;
-    const V4 h = LP(0, size);
+    const V4 h = SEG ? V4{HDR0, HDR1, sg->n0, sg->n1} : LP(0, size);
     if (size < 8u || h.x != HDR0 || (h.y & 0x00ffffffu) != (HDR1 & 0x00ffffffu))
         early = CZ_STATUS_COMMAND;
     else if (size < 33u)
         early = CZ_STATUS_MALFORMED;
     const u32 n0 = h.z, n1 = h.w;
-    if (early == CZ_STATUS_OK) {
+    if (!SEG && early == CZ_STATUS_OK) {
         const u64 nonce = ((u64)bswap32(n0) << 32) | (u64)bswap32(n1);
         *nonce_out = nonce;
         if (check_floor && (long long)nonce <= floor)
@@ -86,14 +101,19 @@ __device__ __forceinline__ u32 relay_frame(const uint8_t *in, u32 size, const u3
 
     const u32 nblk = (size + 63u) >> 6;
     const u32 nfull = size >> 6;
+    // SEG: box blocks [b0, bend); first: this lane holds block 0
+    const u32 b0 = SEG ? sg->b0 : 0u;
+    const u32 bend = SEG && sg->b1 < nblk ? sg->b1 : nblk;
+    const bool first = !SEG || b0 == 0u;
+    u32 mpoly = 0;  // SEG: 16-byte Poly1305 blocks absorbed, the same on both sides (open_segment's count)
     u32 x[16], C[16];
     Poly Pi, Po;
 
     // block 0: keystream bytes 0..31 key the MACs, box bytes 32..63 are the flags byte and payload
     salsa20_block<true>(x, kin, n0, n1, 0u, 0u);
     poly_init(Pi, x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7]);
-    const V4 tin = LP(16, size - 16u);
-    {
+    const V4 tin = first ? LP(16, size - 16u) : zero4();
+    if (first) {
         const V4 a = LP(32, size - 32u);
         const V4 b = LP(48, size > 48u ? size - 48u : 0u);
         C[8] = a.x; C[9] = a.y; C[10] = a.z; C[11] = a.w;
@@ -115,21 +135,28 @@ __device__ __forceinline__ u32 relay_frame(const uint8_t *in, u32 size, const u3
             }
         }
     };
-    poly_block0(Pi);
+    if (first) {
+        poly_block0(Pi);
 #pragma unroll
-    for (int k = 8; k < 16; k++)
-        C[k] ^= x[k];  // plaintext, in registers only
-    *flags_out = C[8] & 0xffu;
-    C[8] &= 0xffffff00u | (CZ_MSG_MORE | CZ_MSG_COMMAND);
+        for (int k = 8; k < 16; k++)
+            C[k] ^= x[k];  // plaintext, in registers only
+        *flags_out = C[8] & 0xffu;
+        C[8] &= 0xffffff00u | (CZ_MSG_MORE | CZ_MSG_COMMAND);
+        if constexpr (SEG)
+            mpoly = ((size < 64u ? size : 64u) - 32u + 15u) >> 4;
+    }
     salsa20_block<true>(x, kout, m0, m1, 0u, 0u);
     poly_init(Po, x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7]);
+    if (first) {
 #pragma unroll
-    for (int k = 8; k < 16; k++)
-        C[k] ^= x[k];
-    poly_block0(Po);
-    C[0] = HDR0; C[1] = HDR1; C[2] = m0; C[3] = m1;
-    C[4] = C[5] = C[6] = C[7] = 0u;  // tag slot, written by em.tag()
-    em.emit(0, C);
+        for (int k = 8; k < 16; k++)
+            C[k] ^= x[k];
+        poly_block0(Po);
+        C[0] = HDR0; C[1] = HDR1; C[2] = m0; C[3] = m1;
+        C[4] = C[5] = C[6] = C[7] = 0u;  // tag slot, written by em.tag() (SEG: or by the combine)
+    }
+    if constexpr (!SEG)
+        em.emit(0, C);
 
     // Poly1305 over block blk's ciphertext in C (tailv of its 64 bytes are body)
     auto poly_blockn = [&](Poly &P, bool full, u32 tailv) {
@@ -152,60 +179,96 @@ __device__ __forceinline__ u32 relay_frame(const uint8_t *in, u32 size, const u3
             }
         }
     };
-    for (u32 blk = 1; blk < nblk; blk++) {
+    for (u32 blk = SEG ? b0 : 1u; blk < bend; blk++) {
         const bool full = blk < nfull;
         const u32 o = 64u * blk, tailv = size - o;
-        V4 q0, q1, q2, q3;
-        if (full) {
-            q0 = LF(o);
-            q1 = LF(o + 16u);
-            q2 = LF(o + 32u);
-            q3 = LF(o + 48u);
-        } else {
-            q0 = LP(o, tailv);
-            q1 = LP(o + 16u, tailv > 16u ? tailv - 16u : 0u);
-            q2 = LP(o + 32u, tailv > 32u ? tailv - 32u : 0u);
-            q3 = LP(o + 48u, tailv > 48u ? tailv - 48u : 0u);
+        if (!SEG || blk != 0u) {
+            V4 q0, q1, q2, q3;
+            if (full) {
+                q0 = LF(o);
+                q1 = LF(o + 16u);
+                q2 = LF(o + 32u);
+                q3 = LF(o + 48u);
+            } else {
+                q0 = LP(o, tailv);
+                q1 = LP(o + 16u, tailv > 16u ? tailv - 16u : 0u);
+                q2 = LP(o + 32u, tailv > 32u ? tailv - 32u : 0u);
+                q3 = LP(o + 48u, tailv > 48u ? tailv - 48u : 0u);
+            }
+            C[0] = q0.x; C[1] = q0.y; C[2] = q0.z; C[3] = q0.w;
+            C[4] = q1.x; C[5] = q1.y; C[6] = q1.z; C[7] = q1.w;
+            C[8] = q2.x; C[9] = q2.y; C[10] = q2.z; C[11] = q2.w;
+            C[12] = q3.x; C[13] = q3.y; C[14] = q3.z; C[15] = q3.w;
+            // a last block of at most 16 body bytes: keystream words 0..3 only, on both sides (the bytes
+            // of words 4..15 are past the body: masked by Poly1305's partial block and by the emitter)
+            const bool w03 = !full && tailv <= 16u;
+            if (w03)
+                salsa20_block_w03<true>(x, kin, n0, n1, blk, 0u);
+            else
+                salsa20_block<true>(x, kin, n0, n1, blk, 0u);
+            poly_blockn(Pi, full, tailv);
+#pragma unroll
+            for (int k = 0; k < 16; k++)
+                C[k] ^= x[k];
+            if (w03)
+                salsa20_block_w03<true>(x, kout, m0, m1, blk, 0u);
+            else
+                salsa20_block<true>(x, kout, m0, m1, blk, 0u);
+#pragma unroll
+            for (int k = 0; k < 16; k++)
+                C[k] ^= x[k];
+            poly_blockn(Po, full, tailv);
+            if constexpr (SEG)
+                mpoly += full ? 4u : (tailv + 15u) >> 4;
         }
-        C[0] = q0.x; C[1] = q0.y; C[2] = q0.z; C[3] = q0.w;
-        C[4] = q1.x; C[5] = q1.y; C[6] = q1.z; C[7] = q1.w;
-        C[8] = q2.x; C[9] = q2.y; C[10] = q2.z; C[11] = q2.w;
-        C[12] = q3.x; C[13] = q3.y; C[14] = q3.z; C[15] = q3.w;
-        // a last block of at most 16 body bytes: keystream words 0..3 only, on both sides (the bytes
-        // of words 4..15 are past the body: masked by Poly1305's partial block and by the emitter)
-        const bool w03 = !full && tailv <= 16u;
-        if (w03)
-            salsa20_block_w03<true>(x, kin, n0, n1, blk, 0u);
-        else
-            salsa20_block<true>(x, kin, n0, n1, blk, 0u);
-        poly_blockn(Pi, full, tailv);
-#pragma unroll
-        for (int k = 0; k < 16; k++)
-            C[k] ^= x[k];
-        if (w03)
-            salsa20_block_w03<true>(x, kout, m0, m1, blk, 0u);
-        else
-            salsa20_block<true>(x, kout, m0, m1, blk, 0u);
-#pragma unroll
-        for (int k = 0; k < 16; k++)
-            C[k] ^= x[k];
-        poly_blockn(Po, full, tailv);
-        if (full)
+        if constexpr (SEG)
+            em.emit(blk - b0, C);  // (block 0 of a first segment: C as left above)
+        else if (full)
             em.emit_full(blk, C);
         else
             em.emit(blk, C);
     }
 
-    u32 tag[4];
-    poly_finish(Pi, tag);
-    const u32 diff = (tag[0] ^ tin.x) | (tag[1] ^ tin.y) | (tag[2] ^ tin.z) | (tag[3] ^ tin.w);
-    poly_finish(Po, tag);
-    em.tag(tag);
+    // (one tag() / close() site: a cooperative wave may hold whole frames and segments side by side)
+    u32 diff = 0;
+    if (!SEG || !sg->rec_in) {
+        u32 tag[4];
+        poly_finish(Pi, tag);
+        diff = (tag[0] ^ tin.x) | (tag[1] ^ tin.y) | (tag[2] ^ tin.z) | (tag[3] ^ tin.w);
+        poly_finish(Po, tag);
+        em.tag(tag);
+    }
     // never leave a sealed copy of unauthenticated plaintext; converged for cooperative emitters
     em.close(dead || diff != 0);
+    if constexpr (SEG) {
+        if (sg->rec_in) {
+            u32 *ri = sg->rec_in, *ro = sg->rec_out;
+            ri[0] = Pi.h0; ri[1] = Pi.h1; ri[2] = Pi.h2; ri[3] = Pi.h3; ri[4] = Pi.h4; ri[5] = mpoly;
+            ro[0] = Po.h0; ro[1] = Po.h1; ro[2] = Po.h2; ro[3] = Po.h3; ro[4] = Po.h4; ro[5] = mpoly;
+            if (first) {
+                ri[6] = *flags_out;
+                ri[8] = Pi.r0; ri[9] = Pi.r1; ri[10] = Pi.r2; ri[11] = Pi.r3;
+                ri[12] = Pi.p0; ri[13] = Pi.p1; ri[14] = Pi.p2; ri[15] = Pi.p3;
+                ro[8] = Po.r0; ro[9] = Po.r1; ro[10] = Po.r2; ro[11] = Po.r3;
+                ro[12] = Po.p0; ro[13] = Po.p1; ro[14] = Po.p2; ro[15] = Po.p3;
+            }
+            return CZ_STATUS_OK;
+        }
+    }
     if (dead)
         return early;
     return diff != 0 ? (u32)CZ_STATUS_CRYPTO : (u32)CZ_STATUS_OK;
+}
+
+// RELAY box blocks [b0, b1) of one body whose header passed open_header: relay_frame's SEG form
+template <bool AL, class EM>
+__device__ __forceinline__ u32 relay_segment(const uint8_t *in, u32 size, const u32 kin[8], u32 n0, u32 n1,
+                                             const u32 kout[8], u64 counter_out, u32 b0, u32 b1, u32 *rec_in,
+                                             u32 *rec_out, u32 &flags_out, EM &em)
+{
+    const RelaySeg sg{n0, n1, b0, b1, rec_in, rec_out};
+    u64 nonce = 0;
+    return relay_frame<AL, EM, 16, true>(in, size, kin, false, 0, kout, counter_out, &flags_out, &nonce, em, &sg);
 }
 
 // One lane of a relay whose output is stored lane by lane: AL code paths when body and output both
@@ -308,4 +371,140 @@ __global__ __launch_bounds__(BLOCK) CZ_RELAY_OCC void k_relay_uniform(
             zero_bytes(dst + size, (u32)(out_stride - size));
     }
     status[i] = (uint16_t)(st | (st == CZ_STATUS_OK ? (fl << 8) : 0u));
+}
+
+// ---- segmented relay (header section 3i): long bodies re-sealed across lanes ----------------------
+// waves per SIMD of k_relay_segments: two keys, two keystream blocks and two Poly1305 chains per lane, as
+// k_relay_desc (189 VGPRs); DESIGN.md section 4 "Segmented relay" records what this compiles to
+#ifndef CZ_RELAY_SEG_WAVES_PER_EU
+#define CZ_RELAY_SEG_WAVES_PER_EU 2
+#endif
+#define CZ_RELAY_SEG_OCC __attribute__((amdgpu_waves_per_eu(CZ_RELAY_SEG_WAVES_PER_EU, CZ_RELAY_SEG_WAVES_PER_EU)))
+
+// cz_relay_segments: one lane per segment, structured as k_open_segments.  Every lane runs open_header
+// for its frame (floor from desc[prev]'s body in `in`); the lane with block 0 writes the nonce, rec[7] =
+// early for the combine, and an early status.  work: two planes of npart records, the inbound partial
+// of part p at record p (open_segment's layout), the outbound one at record npart + p.
+// A full wave of segments with one chunk count, bodies and outputs on 16 bytes and no rejected lane
+// takes a seal line emitter (EmitSegLines, or with SEGMODE_SHIFT16 and outputs off the 128-byte lines
+// EmitShiftLines); every other wave stores lane by lane, byte-exact at any alignment of either side.
+// A frame rejected before decryption: each of its segments zeroes its own byte range.
+__global__ __launch_bounds__(BLOCK) CZ_RELAY_SEG_OCC void k_relay_segments(
+    const cz_frame_desc *__restrict__ desc, const cz_fanout_sub *__restrict__ to, const cz_segment *__restrict__ segs,
+    uint32_t nseg, const uint8_t *__restrict__ in, uint8_t *__restrict__ out, const uint8_t *__restrict__ subkeys,
+    u32 *__restrict__ work, uint32_t npart, uint16_t *__restrict__ status, uint64_t *__restrict__ nonces, int mode)
+{
+    extern __shared__ uint4 smem[];
+    const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
+    const uint32_t wave_first = t & ~63u;
+    if (wave_first >= nseg)
+        return;
+    const bool live = t < nseg;
+    const cz_segment sg = segs[live ? t : wave_first];
+    const cz_frame_desc d = desc[sg.frame];
+    const cz_fanout_sub sb = to[sg.frame];
+    long long floor = (long long)d.counter;
+    if (d.prev >= 0)
+        floor = (long long)read_be64(in + desc[d.prev].in_off + 8);
+    const uint8_t *src = in + d.in_off;
+    u32 n0 = 0, n1 = 0;
+    u64 nonce = 0;
+    const u32 early = open_header(src, d.len, (d.flags & CZ_DESC_CHECK_NONCE) != 0, floor, n0, n1, nonce);
+    u32 *rec_in = sg.part == 0xffffffffu ? nullptr : work + 16ull * sg.part;
+    u32 *rec_out = rec_in ? rec_in + 16ull * npart : nullptr;
+    if (live && sg.first_block == 0) {
+        if (nonces)
+            nonces[sg.frame] = nonce;
+        if (rec_in)
+            rec_in[7] = early;  // the combine kernel finishes frames whose header passed
+        if (early != CZ_STATUS_OK)
+            status[sg.frame] = (uint16_t)early;
+    }
+    // this segment's bytes: box blocks [first_block, bend) of the body, clipped to its size
+    const u32 nblk = (d.len + 63u) >> 6;
+    const u32 b1 = sg.first_block + sg.nblocks;
+    const u32 bend = b1 < nblk ? b1 : nblk;
+    const u64 end = 64ull * bend < d.len ? 64ull * bend : d.len;
+    const u32 total = end > 64ull * sg.first_block ? (u32)(end - 64ull * sg.first_block) : 0u;
+    const u32 nch = (total + 63u) >> 6;
+    uint8_t *dst = out + d.out_off + 64ull * sg.first_block;
+    const bool al = aligned16(src, dst);
+    u32 key_in[8], key_out[8];
+    load_key(subkeys + 32ull * d.key_idx, key_in);
+    load_key(subkeys + 32ull * sb.key_idx, key_out);
+    u32 fl = 0, st;
+    if ((mode & SEGMODE_LINES) && wave_lines_ok(wave_first + 64u <= nseg, nch, al) &&
+        __builtin_amdgcn_ballot_w64(early != CZ_STATUS_OK || nch == 0u) == 0) {
+        const u32 lane = threadIdx.x & 63u;
+        uint8_t *wl = reinterpret_cast<uint8_t *>(smem) + (threadIdx.x >> 6) * SHIFT_LDS_BYTES;
+        const bool line_al = (((uintptr_t)dst) & 127u) == 0;  // as in seal_segments_body
+        if (!(mode & SEGMODE_SHIFT16) || __builtin_amdgcn_ballot_w64(!line_al) == 0) {
+            EmitSegLinesSeal em{reinterpret_cast<uint4 *>(wl), dst, lane, total, 0u, 0u};
+            em.init(sg.first_block == 0);
+            st = relay_segment<true>(src, d.len, key_in, n0, n1, key_out, sb.counter, sg.first_block, b1, rec_in,
+                                     rec_out, fl, em);
+        } else {
+            EmitShiftLinesSeal em{wl, dst, lane, total, 0u, 0u};
+            em.init(sg.first_block == 0);
+            st = relay_segment<true>(src, d.len, key_in, n0, n1, key_out, sb.counter, sg.first_block, b1, rec_in,
+                                     rec_out, fl, em);
+        }
+    } else {
+        if (!live)
+            return;
+        if (early != CZ_STATUS_OK || nch == 0u) {
+            zero_bytes(dst, total);  // rejected before decryption: zeros over this segment's bytes
+            return;
+        }
+        if (al) {
+            EmitDirect<true> em{dst, total};
+            st = relay_segment<true>(src, d.len, key_in, n0, n1, key_out, sb.counter, sg.first_block, b1, rec_in,
+                                     rec_out, fl, em);
+        } else {
+            EmitDirect<false> em{dst, total};
+            st = relay_segment<false>(src, d.len, key_in, n0, n1, key_out, sb.counter, sg.first_block, b1, rec_in,
+                                      rec_out, fl, em);
+        }
+    }
+    if (!rec_in)
+        status[sg.frame] = (uint16_t)(st | (st == CZ_STATUS_OK ? (fl << 8) : 0u));
+}
+
+// One lane per split frame: combine_tag over the inbound plane against the received tag; a match
+// joins the outbound plane into the tag slot the segments left, a mismatch zeroes the whole body
+// (16-byte stores over the aligned interior, as k_open_combine) -- no sealed copy of unauthenticated
+// plaintext outlives this kernel.  A frame rejected before decryption (rec[7]) is finished already.
+__global__ __launch_bounds__(BLOCK) void k_relay_combine(const cz_frame_desc *__restrict__ desc,
+                                                          const cz_combine *__restrict__ comb, uint32_t ncomb,
+                                                          const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
+                                                          const u32 *__restrict__ work, uint32_t npart,
+                                                          uint16_t *__restrict__ status)
+{
+    const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= ncomb)
+        return;
+    const cz_combine cb = comb[t];
+    const u32 *Ri = work + 16ull * cb.part0;
+    if (Ri[7] != CZ_STATUS_OK)
+        return;
+    const cz_frame_desc d = desc[cb.frame];
+    u32 tag[4];
+    combine_tag(Ri, cb.nseg, tag);
+    const uint8_t *tp = in + d.in_off + 16;
+    u32 tin[4];
+    for (int w = 0; w < 4; w++)
+        tin[w] = (u32)tp[4 * w] | ((u32)tp[4 * w + 1] << 8) | ((u32)tp[4 * w + 2] << 16) |
+                 ((u32)tp[4 * w + 3] << 24);
+    if ((tag[0] ^ tin[0]) | (tag[1] ^ tin[1]) | (tag[2] ^ tin[2]) | (tag[3] ^ tin[3])) {
+        zero_bytes(out + d.out_off, d.len);
+        status[cb.frame] = CZ_STATUS_CRYPTO;
+        return;
+    }
+    combine_tag(Ri + 16ull * npart, cb.nseg, tag);
+    uint8_t *dst = out + d.out_off + 16;
+    if ((((uintptr_t)dst) & 15u) == 0)
+        st16<true>(dst, tag[0], tag[1], tag[2], tag[3]);
+    else
+        st16<false>(dst, tag[0], tag[1], tag[2], tag[3]);
+    status[cb.frame] = (uint16_t)(CZ_STATUS_OK | (Ri[6] << 8));
 }

@@ -7,10 +7,10 @@ arguments; tools/dispatch_record/driver.cpp calls the launchers over a grid of l
 counts and knob settings.  The kernel names are normalised (enum names to values, defaulted template
 arguments filled in), so two spellings of one instantiation record the same text.
 
-    python tools/dispatch_record.py [--csrc DIR] [-o FILE] [--relay]
+    python tools/dispatch_record.py [--csrc DIR] [-o FILE] [--relay | --relay-segments]
 
---relay records the relay launcher's grid (czk_relay_uniform) instead; the default grid, and with it
-the parent's record, does not hold those cases.
+--relay records the relay launcher's grid (czk_relay_uniform) instead, --relay-segments the segmented
+relay's (czk_relay_segments); the default grid, and with it the parent's record, holds neither.
 
 tests/golden/dispatch_parent.txt is the record of the commit before the launchers were rebuilt on
 cz_dispatch.h; tests/test_dispatch_record.py requires the working tree to record the same text.
@@ -64,9 +64,11 @@ def signatures(text):
     return {ln[2:].split(" g=", 1)[0] for ln in text.splitlines() if ln.startswith("  ") and " g=" in ln}
 
 
-def record(csrc=CSRC, relay=False):
-    """Build the recorder against `csrc`/cz_kernels.hip, run it (relay: over the relay launcher's grid
-    instead of the default one), return the normalised record."""
+def record(csrc=CSRC, relay=False, relay_segments=False):
+    """Build the recorder against `csrc`/cz_kernels.hip, run it (relay / relay_segments: over that
+    launcher's grid instead of the default one), return the normalised record."""
+    if relay and relay_segments:
+        raise ValueError("one grid per record: relay or relay_segments")
     with tempfile.TemporaryDirectory(prefix="cz_dispatch_") as td:
         exe = os.path.join(td, "dispatch_record")
         cmd = [HIPCC, "--offload-arch=gfx950", "--offload-host-only", "-std=c++17", "-O1", "-w",
@@ -76,7 +78,7 @@ def record(csrc=CSRC, relay=False):
         r = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True)
         if r.returncode:
             raise RuntimeError(f"{' '.join(cmd)}\n{r.stderr[-4000:]}")
-        raw = subprocess.run([exe] + (["relay"] if relay else []), capture_output=True, text=True, check=True).stdout
+        raw = subprocess.run([exe] + (["relay"] if relay else ["relay_segments"] if relay_segments else []), capture_output=True, text=True, check=True).stdout
     return normalise(raw)
 
 
@@ -85,8 +87,10 @@ def main():
     ap.add_argument("--csrc", default=CSRC, help="the directory holding cz_kernels.hip (default: this tree's)")
     ap.add_argument("-o", "--output", help="write the record here instead of standard output")
     ap.add_argument("--relay", action="store_true", help="record the relay launcher's grid instead of the default one")
+    ap.add_argument("--relay-segments", action="store_true",
+                    help="record the segmented relay launcher's grid instead of the default one")
     a = ap.parse_args()
-    text = record(a.csrc, a.relay)
+    text = record(a.csrc, a.relay, a.relay_segments)
     if a.output:
         with open(a.output, "w") as f:
             f.write(text)

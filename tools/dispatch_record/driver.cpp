@@ -32,6 +32,10 @@ int czk_tune(const char *, int);
 // (weak: a revision of csrc/ from before the relay still links, and records no relay case)
 hipError_t czk_relay_uniform(const void *, uint64_t, void *, uint64_t, uint32_t, uint32_t, const void *, uint64_t, int,
                              const void *, uint64_t, uint16_t *, hipStream_t) __attribute__((weak));
+// (weak for the same reason: a revision from before the segmented relay records no relay_segments case)
+hipError_t czk_relay_segments(const cz_frame_desc *, const cz_fanout_sub *, const cz_segment *, uint32_t,
+                              const cz_combine *, uint32_t, uint32_t, const void *, void *, const void *, void *,
+                              uint16_t *, uint64_t *, hipStream_t) __attribute__((weak));
 }
 
 namespace {
@@ -316,6 +320,26 @@ void relay_cases()
     }
 }
 
+// The segmented relay's grid (`dispatch_record.py --relay-segments`; not part of the default record):
+// segment counts around a workgroup, with and without split frames, every knob
+void relay_segments_cases()
+{
+    if (!czk_relay_segments)
+        return;
+    for (const Knob &k : KNOBS) {
+        WithKnob w(k);
+        for (uint32_t nseg : {0u, 1u, 255u, 256u, 257u, 1025u, 1u << 20})
+            for (uint32_t ncomb : {0u, 1u, 256u, 257u}) {
+                const uint32_t npart = 2u * ncomb;
+                std::printf("relay_segments nseg=%u ncomb=%u npart=%u\n", nseg, ncomb, npart);
+                result(czk_relay_segments(ptr<cz_frame_desc>(AUX), ptr<cz_fanout_sub>(AUX + 2048), ptr<cz_segment>(AUX + 4096),
+                                          nseg, ptr<cz_combine>(AUX + 8192), ncomb, npart, ptr<void>(IN), ptr<void>(OUT),
+                                          ptr<void>(KEY), ptr<void>(AUX + 12288), ptr<uint16_t>(AUX + 16384),
+                                          ptr<uint64_t>(AUX + 20480), nullptr));
+            }
+    }
+}
+
 // czk_tune: the old value it returns, what a value is clamped to, an unknown key
 void tune_cases()
 {
@@ -333,6 +357,10 @@ int main(int argc, char **argv)
 {
     if (argc > 1 && std::string(argv[1]) == "relay") {
         relay_cases();
+        return 0;
+    }
+    if (argc > 1 && std::string(argv[1]) == "relay_segments") {
+        relay_segments_cases();
         return 0;
     }
     seal_cases();

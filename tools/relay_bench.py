@@ -15,6 +15,15 @@ Host-staged leg (pinned torch tensors, one stream, a host clock ending in a sync
   relay     H2D bodies -> cz_relay_uniform -> D2H bodies
   two-call  H2D bodies -> open -> D2H payloads -> H2D payloads -> seal -> D2H bodies
 
+--segments measures the segmented relay (cz_relay_segments, header section 3i) instead and writes
+profiles/relay/relay_segments.json; the legs above and relay.json are not touched.  Three sides alternate, all
+at seg_blocks = batch.SEG_BLOCKS:
+  A  cz_relay_segments on the cz_plan_segments(open = 1) plan
+  B  cz_relay_batch with cz_plan_order (one lane per frame, longest first)
+  C  cz_open_segments, then cz_seal_segments
+over 1024 bodies of 65569 bytes under 1024 key pairs; 2^16 frames of the Zipf 64 B .. 64 KiB length mix of
+bench.py's zipf config; 2^16 bodies of 1 KiB payload (nothing is split).  16-byte aligned slots.
+
 Writes profiles/relay/relay.json and prints it.  --log2 / --batch-log2 / --host-log2 shrink the shapes for a
 rehearsal; the committed file is measured at the defaults.  --pmc: one call of each side at the first uniform
 shape, for a counter run:
@@ -177,6 +186,114 @@ def batch_leg(args, torch, dev, batch):
     return finish(row, count * size)
 
 
+SEGMENT_KERNELS = ["k_relay_segments", "k_relay_combine", "k_relay_desc"]
+
+
+def zipf_lengths(frames):
+    """bench.py's zipf config: payload lengths 64 j, j ~ Zipf(1.2) on 1..1024, seed 42"""
+    rng = np.random.default_rng(42)
+    j = np.empty(0, dtype=np.int64)
+    while len(j) < frames:
+        z = rng.zipf(1.2, size=frames)
+        j = np.concatenate([j, z[z <= 1024]])
+    return (64 * j[:frames]).astype(np.uint64)
+
+
+def segments_leg(args, torch, dev, batch, name, lengths):
+    """payload lengths -> bodies sealed under 1024 inbound keys in 16-byte aligned slots, then the three sides"""
+    count, pairs = len(lengths), 1024
+    lengths = np.asarray(lengths, dtype=np.uint64)
+    sizes = lengths + np.uint64(33)
+    off = lambda ln: np.concatenate([[0], np.cumsum((ln + np.uint64(15)) // np.uint64(16) * np.uint64(16))]).astype(np.uint64)  # noqa: E731
+    poff, boff = off(lengths), off(sizes)
+    keys = torch.empty(2 * pairs * 32, dtype=torch.uint8, device=dev)
+    batch.fill(keys, 7)
+    keys = keys.view(2 * pairs, 32)
+    idx = np.arange(count, dtype=np.uint64)
+    k_in = (2 * (idx % pairs)).astype(np.uint32)
+    k_out = (2 * ((idx * 7 + 1) % pairs) + 1).astype(np.uint32)
+    plain = torch.empty(int(poff[-1]) + 64, dtype=torch.uint8, device=dev)
+    batch.fill(plain, 13)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)  # noqa: E731
+    sb = batch.SEG_BLOCKS
+    # the received bodies: sealed under the inbound keys
+    sd = np.zeros(count, dtype=batch.DESC_DTYPE)
+    sd["in_off"], sd["out_off"], sd["len"], sd["key_idx"] = poff[:-1], boff[:-1], lengths, k_in
+    sd["counter"], sd["prev"] = idx + 100, -1
+    bodies = torch.zeros(int(boff[-1]) + 64, dtype=torch.uint8, device=dev)
+    batch.seal_segments(up(sd), batch.SegmentPlan(sd, open_=False, seg_blocks=sb).to(dev), plain, bodies, keys, desc_np=sd)
+    # relay / open descriptors (the same records), the outbound records, and side C's seal descriptors
+    od = np.zeros(count, dtype=batch.DESC_DTYPE)
+    od["in_off"], od["len"], od["key_idx"], od["counter"] = boff[:-1], sizes, k_in, idx + 99
+    od["flags"], od["prev"] = 0x100, -1
+    rd = od.copy()
+    rd["out_off"] = boff[:-1]
+    od["out_off"] = poff[:-1]
+    to = np.zeros(count, dtype=batch.FANOUT_SUB_DTYPE)
+    to["counter"], to["key_idx"] = idx + (1 << 40), k_out
+    td = sd.copy()
+    td["key_idx"], td["counter"] = k_out, to["counter"]
+    d_rd, d_od, d_to, d_td = up(rd), up(od), up(to), up(td)
+    plan_a = batch.SegmentPlan(rd, open_=True, seg_blocks=sb).to(dev, records=2)
+    plan_o = batch.SegmentPlan(od, open_=True, seg_blocks=sb).to(dev)
+    plan_s = batch.SegmentPlan(td, open_=False, seg_blocks=sb).to(dev)
+    d_order = torch.from_numpy(batch.plan_order(rd).view(np.int32)).to(dev)
+    outs = [torch.zeros(int(boff[-1]) + 64, dtype=torch.uint8, device=dev) for _ in range(3)]
+    sts = [torch.full((count,), -1, dtype=torch.int16, device=dev) for _ in range(3)]
+
+    def side_a():
+        batch.relay_segments(d_rd, d_to, plan_a, bodies, outs[0], keys, sts[0])
+
+    def side_b():
+        batch.relay_batch(d_rd, d_to, count, bodies, outs[1], keys, sts[1], order=d_order)
+
+    def side_c():
+        batch.open_segments(d_od, plan_o, bodies, plain, keys, sts[2])
+        batch.seal_segments(d_td, plan_s, plain, outs[2], keys)
+
+    batch.relay_segments(d_rd, d_to, plan_a, bodies, outs[0], keys, sts[0], desc_np=rd, to_np=to)      # bounds, once
+    side_b()
+    side_c()
+    torch.cuda.synchronize()
+    assert all(int((st != 0).sum()) == 0 for st in sts), "a body was rejected"
+    assert torch.equal(outs[0], outs[1]), "cz_relay_segments and cz_relay_batch disagree"
+    assert torch.equal(outs[0], outs[2]), "cz_relay_segments and open_segments + seal_segments disagree"
+    body_bytes = int(sizes.sum())
+    row = {"leg": name, "count": count, "body_bytes": body_bytes, "max_size": int(sizes.max()), "key_pairs": pairs,
+           "seg_blocks": sb, "segments": plan_a.nseg, "split_frames": plan_a.ncomb}
+    row.update(alternate(torch, event_ms, {"segments": side_a, "batch": side_b, "open_seal": side_c}, args.reps))
+    row["a_over_b"] = round(row["segments_ms"] / row["batch_ms"], 4)
+    row["a_over_c"] = round(row["segments_ms"] / row["open_seal_ms"], 4)
+    for k in ("segments", "batch", "open_seal"):
+        row[k + "_gib_s"] = round(body_bytes / 2**30 / (row[k + "_ms"] * 1e-3), 1)
+    return row
+
+
+def segments_main(args, torch, dev, batch, build, _lib):
+    out = {"device": torch.cuda.get_device_name(0), "library": _lib.lib().cz_version().decode(),
+           "relay_kernels_sha256": build.kernel_code_sha256(_lib.LIB_PATH, SEGMENT_KERNELS), "reps": args.reps,
+           "sides": {"segments": "A: cz_relay_segments", "batch": "B: cz_relay_batch with cz_plan_order",
+                     "open_seal": "C: cz_open_segments then cz_seal_segments"},
+           "clock_device": "hipEvent (torch.cuda.Event) around one call of each side, median of the alternations",
+           "spread": "(max - min) / median of a side's alternations", "legs": []}
+    path = args.out if args.out else os.path.join(ROOT, "profiles", "relay", "relay_segments.json")
+    n = 1 << args.seg_log2
+    shapes = (("64k_x_1024", np.full(min(1024, n), 65536, dtype=np.uint64)), ("zipf", zipf_lengths(n)),
+              ("1k_unsplit", np.full(n, 1024, dtype=np.uint64)))
+    for name, lengths in shapes:
+        out["legs"].append(segments_leg(args, torch, dev, batch, name, lengths))
+        torch.cuda.empty_cache()
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+    for r in out["legs"]:
+        print(f"{r['leg']}: A {r['segments_ms']} ms, B {r['batch_ms']} ms, C {r['open_seal_ms']} ms, A/B {r['a_over_b']}, "
+              f"A/C {r['a_over_c']}", file=sys.stderr)
+    print(json.dumps({k: v for k, v in out.items() if k != "legs"} |
+                     {"legs": [{k: v for k, v in r.items() if not k.endswith("_all_ms")} for r in out["legs"]]}))
+
+
 def host_leg(args, torch, dev, batch):
     count, size, ist, pst = 1 << args.host_log2, 4129, 4224, 4096
     keys = torch.empty(64, dtype=torch.uint8, device=dev)
@@ -221,23 +338,31 @@ def host_leg(args, torch, dev, batch):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--reps", type=int, default=12, help="alternations per leg (at least 10)")
+    ap.add_argument("--reps", type=int, default=12, help="alternations per leg (at least 10; --segments: at least 12)")
     ap.add_argument("--log2", type=int, default=20, help="uniform legs: log2 of the frame count")
     ap.add_argument("--batch-log2", type=int, default=16)
     ap.add_argument("--host-log2", type=int, default=16)
     ap.add_argument("--pmc", action="store_true",
                     help="one call of each side at the first uniform shape and nothing else: the run to put under "
                          "rocprofv3 --pmc SQ_INSTS_VALU (counters in a run of their own, no tracing)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "relay", "relay.json"))
+    ap.add_argument("--segments", action="store_true",
+                    help="measure cz_relay_segments against cz_relay_batch and open_segments + seal_segments instead; "
+                         "writes profiles/relay/relay_segments.json")
+    ap.add_argument("--seg-log2", type=int, default=16, help="--segments: log2 of the frame count of the ragged legs")
+    ap.add_argument("--out", default=None, help="default: profiles/relay/relay.json (relay_segments.json with --segments)")
     args = ap.parse_args()
-    if args.reps < 10:
-        ap.error("--reps: at least 10 alternations")
+    if args.reps < (12 if args.segments else 10):
+        ap.error("--reps: at least 10 alternations (--segments: 12)")
     import torch
 
     from jeromq_amd import _lib, batch, build
     if not torch.cuda.is_available():
         raise SystemExit("relay_bench needs a GPU")
     dev = torch.device("cuda:0")
+    if args.segments:
+        segments_main(args, torch, dev, batch, build, _lib)
+        return
+    args.out = args.out or os.path.join(ROOT, "profiles", "relay", "relay.json")
     if args.pmc:
         uniform_leg(args, torch, dev, batch, *UNIFORM_SHAPES[0], once=True)
         return
