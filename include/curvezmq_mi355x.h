@@ -757,6 +757,55 @@ int cz_open_streams(const cz_v2_stream *d_streams, uint32_t count, const void *d
                     void *d_out, uint64_t out_cap, const void *d_subkeys, uint16_t *d_status, uint64_t *d_nonces,
                     cz_v2_totals *h_totals, void *stream);
 
+/* ---- 3j. stream relay: received V2 streams re-sealed wire to wire (placed here for section 7b's records) ----
+ * Sections 3h and 7b together, for a broker's received byte streams.  A re-sealed body has the size and layout
+ * of the received one, so the V2 header in front of it stays valid: a received wire stream whose bodies are
+ * re-sealed where they lie IS the outbound wire stream.  Replaces Proxy.forward (zmq/Proxy.java:140-160) per
+ * message: V2Decoder (V2Decoder.java:37-105, Decoder.java:76-98) and Mechanism.decode
+ * (CurveServerMechanism.java:165-225 / CurveClientMechanism.java:165-224) on one StreamEngine, Mechanism.encode
+ * (:126-163) and V2Encoder (V2Encoder.java:31-55) on another.
+ *
+ * d_streams[s] is section 7b's record (bytes, floor, inbound key).  d_to[s] = {counter, key_idx}: the outbound
+ * cnNonce of the stream's first frame and the outbound subkey.  Frame k of the stream is sealed with counter + k
+ * (mod 2^64); a rejected frame consumes its counter, cz_relay_uniform's rule (the receiver accepts the gap:
+ * CurveClientMechanism.java:186-193).  Inbound and outbound key and counter may be equal.
+ * THE CHAIN, as cz_open_streams: scan (slot_off / slot_bytes of d_scan and *h_totals mean nothing here), one
+ * synchronisation to read *h_totals, then on `stream` with no further synchronisation: emit -- for frame k of
+ * stream s at index i = first + k, d_desc[i] = {in_off = out_off = the body's offset, len, key_idx, counter =
+ * the frame's replay floor, CZ_DESC_CHECK_NONCE, prev = -1} and d_to_frames[i] = {counter + k, key_idx} --,
+ * cz_relay_batch over those nframes descriptors, and the cut.  The floor of frame k > 0 is the big-endian u64
+ * at bytes [8, 16) of frame k - 1's body, read by the emit before the relay stores anything: that is what makes
+ * the relay legal in place under 3h's rule.  It is read even when that body is shorter than 16 bytes, so d_wire
+ * must be readable for 16 bytes past its last stream (cz_open_streams' rule).
+ * d_out == d_wire: in place.  Otherwise d_out must not overlap d_wire and takes the same offsets; the 2 or 9
+ * header bytes of every whole frame are copied over byte-exact.  No byte of d_out outside the headers and bodies
+ * of whole frames is written: not a trailing partial frame, not the bytes between streams.
+ * d_status[i] / d_nonces[i]: cz_relay_batch's.  An accepted body is, byte for byte, Mechanism.encode's output for
+ * the Msg Mechanism.decode delivers; a rejected frame's body is zeros (3h).
+ * d_results[s]: what of the stream may leave.  Frames behind the first rejected one were relayed by their own
+ * lanes and may sit sealed in d_out: A CALLER SENDS ok_bytes (OR whole_bytes) OF A STREAM AND NOTHING BEHIND THEM.
+ * peer_nonce is cnPeerNonce after the stream by the engine's delivery rule: the wire nonce of the last accepted
+ * frame; the rejected frame's when fail_status == CZ_STATUS_CRYPTO (its nonce passed the replay check before
+ * the tag failed: CurveClientMechanism.java:193); the stream's floor when neither applies.
+ * CZ_ENOMEM with *h_totals filled and nothing written to d_out when nframes > desc_cap (d_desc, d_to_frames,
+ * d_status and d_nonces hold desc_cap records each); CZ_EINVAL above 2^31 - 1 frames.  Null pointers (all are
+ * required, d_nonces included): CZ_EINVAL before the device is touched.  count == 0: CZ_OK, zero totals.  No
+ * device: CZ_EHIP; there is no CPU fallback.  Every frame is one lane of the relay: long frames are correct but
+ * slow. */
+typedef struct cz_relay_stream_result {   /* 32 bytes */
+    uint64_t ok_bytes;      /* wire bytes (headers + bodies) of the frames before the first rejected one */
+    uint64_t whole_bytes;   /* <= ok_bytes: cut back to the end of the last frame whose decrypted flags lack MORE */
+    uint64_t peer_nonce;    /* cnPeerNonce after the stream */
+    uint32_t ok_frames;
+    uint16_t fail_status;   /* CZ_STATUS_* of the first rejected frame, CZ_STATUS_OK when none */
+    uint16_t reserved;      /* 0 */
+} cz_relay_stream_result;
+int cz_relay_streams(const cz_v2_stream *d_streams, const cz_fanout_sub *d_to, uint32_t count,
+                     const void *d_wire, void *d_out, int64_t maxmsgsize,
+                     cz_v2_stream_result *d_scan, cz_frame_desc *d_desc, cz_fanout_sub *d_to_frames,
+                     uint64_t desc_cap, const void *d_subkeys, uint16_t *d_status, uint64_t *d_nonces,
+                     cz_relay_stream_result *d_results, cz_v2_totals *h_totals, void *stream);
+
 /* ---- 8. batching engine: many CURVE connections, one device batch per flush -----------------
  * The GPU form of StreamEngine's encode/decode loops (outEvent: pull + mechanism.encode +
  * V2Encoder up to OUT_BATCH_SIZE, StreamEngine.java:467-535; inEvent: V2Decoder +
@@ -840,6 +889,31 @@ uint64_t cz_engine_fanin_split_frames(const cz_engine *e);
  * and no fan-in routing.  Always one group.  Delivered messages, cnPeerNonce, errors and events are those of
  * the unscanned flush.  Frames of the last cz_engine_flush_in opened this way (0: the path was not taken): */
 uint64_t cz_engine_scan_frames(const cz_engine *e);
+/* Forward routes (section 3j), the broker's Proxy.forward (zmq/Proxy.java:140-160: from.recv, then to.send --
+ * V2Decoder.java:37-105 / Decoder.java:76-98, Mechanism.decode CurveServerMechanism.java:165-225 /
+ * CurveClientMechanism.java:165-224, Mechanism.encode :126-163) without the plaintext ever reaching memory:
+ * everything `from` receives leaves re-sealed for `to`.  ONE SOURCE PER DESTINATION: CZ_EINVAL for an unknown or
+ * removed id, for from == to, and for a `to` that another live route already names; A -> B together with B -> A
+ * is the normal proxy and is legal.  to = -1 clears the route of `from`; removing either end clears it too.
+ * cz_engine_flush_in skips a connection that has a route: its bytes wait for cz_engine_flush_forward. */
+int cz_engine_forward(cz_engine *e, int from, int to);
+/* Every route whose source holds received bytes, in one chain on one stream: the received bytes go over as they
+ * lie with one cz_v2_stream and one cz_fanout_sub per route, cz_relay_streams' chain runs IN PLACE (headers
+ * kept), and the wire bytes and the 32-byte cz_relay_stream_result per route come back into pinned memory: no
+ * per-frame metadata crosses PCIe in either direction.  CUT AT THE FIRST REJECTED FRAME: a route's ok_bytes leave
+ * and nothing behind them; the source then fails exactly as in cz_engine_flush_in (CZ_EPROTO, the event of the
+ * rejected frame's status, its received bytes dropped), and a framing error behind good frames gives the framing
+ * error with event 0.  Otherwise the whole frames leave the receive buffer and a partial frame stays.  The
+ * source's cnPeerNonce becomes the result's peer_nonce; the destination's cnNonce advances by the frames
+ * scanned, as every one consumed a counter.  A route whose destination has failed leaves the source's bytes where
+ * they are and forwards nothing.  cz_engine_flush_out assigns nonces when it runs, so the one ordering rule is:
+ * bytes go to the destination's socket in the order of the flush calls that produced them. */
+int cz_engine_flush_forward(cz_engine *e);
+/* the bytes the last cz_engine_flush_forward made for the destination of `from`'s route: socket-ready wire
+ * frames in pinned memory, valid until the next cz_engine_flush_forward (*len 0: nothing to send) */
+int cz_engine_forward_out(cz_engine *e, int from, const uint8_t **wire, uint64_t *len);
+/* frames the last cz_engine_flush_forward forwarded (the frames inside every route's ok_bytes) */
+uint64_t cz_engine_forward_frames(const cz_engine *e);
 /* decoded messages of the last cz_engine_flush_in (pinned memory, valid until the next one) */
 int cz_engine_msgs_in(cz_engine *e, int conn, uint32_t *count);
 int cz_engine_msg_in(cz_engine *e, int conn, uint32_t i, const uint8_t **payload, uint32_t *len, int *msg_flags);

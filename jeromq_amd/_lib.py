@@ -98,6 +98,14 @@ class cz_v2_totals(ctypes.Structure):
 assert ctypes.sizeof(cz_v2_stream) == 32 and ctypes.sizeof(cz_v2_stream_result) == 32 and ctypes.sizeof(cz_v2_totals) == 16
 
 
+class cz_relay_stream_result(ctypes.Structure):
+    _fields_ = [("ok_bytes", ctypes.c_uint64), ("whole_bytes", ctypes.c_uint64), ("peer_nonce", ctypes.c_uint64),
+                ("ok_frames", ctypes.c_uint32), ("fail_status", ctypes.c_uint16), ("reserved", ctypes.c_uint16)]
+
+
+assert ctypes.sizeof(cz_relay_stream_result) == 32
+
+
 class cz_fanout_sub(ctypes.Structure):
     _fields_ = [("counter", ctypes.c_uint64), ("key_idx", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
@@ -220,6 +228,11 @@ SIGNATURES = {
     "cz_v2_scan": (_I, [_VP, _U32, _VP, ctypes.c_int64, _U32, _VP, _VP, _VP]),
     "cz_v2_scan_emit": (_I, [_VP, _VP, _U32, _VP, _U32, _VP, _VP, _VP]),
     "cz_open_streams": (_I, [_VP, _U32, _VP, ctypes.c_int64, _U32, _VP, _VP, _U64, _VP, _U64, _VP, _VP, _VP, _VP, _VP]),
+    "cz_relay_streams": (_I, [_VP, _VP, _U32, _VP, _VP, ctypes.c_int64, _VP, _VP, _VP, _U64, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "cz_engine_forward": (_I, [_VP, _I, _I]),
+    "cz_engine_flush_forward": (_I, [_VP]),
+    "cz_engine_forward_out": (_I, [_VP, _I, ctypes.POINTER(_VP), ctypes.POINTER(_U64)]),
+    "cz_engine_forward_frames": (_U64, [_VP]),
     "cz_engine_create": (_I, [ctypes.POINTER(_VP), _U64, _I]),
     "cz_engine_destroy": (None, [_VP]),
     "cz_engine_add_conn": (_I, [_VP, _I, _VP, _U64, _U64]),

@@ -521,6 +521,75 @@ def open_streams(streams, wire, results, desc, out, subkeys_t, status, nonces=No
     return rc, int(tot.nframes), int(tot.slot_bytes)
 
 
+RELAY_STREAM_RESULT_DTYPE = np.dtype([("ok_bytes", "<u8"), ("whole_bytes", "<u8"), ("peer_nonce", "<u8"),
+                                      ("ok_frames", "<u4"), ("fail_status", "<u2"), ("reserved", "<u2")])
+assert RELAY_STREAM_RESULT_DTYPE.itemsize == 32
+
+
+def _nbytes(t):
+    return t.numel() * t.element_size()
+
+
+def _check_relay_streams_bounds(count, nto, nscan, nresults, desc_cap, ndesc, nto_frames, nstatus, nnonces, wire_bytes,
+                                out_bytes, streams_np=None, to_np=None, nkeys=None):
+    """One outbound record, scan result and cut result per stream; desc_cap descriptors, outbound records,
+    statuses and nonces per frame; `out` as long as `wire`; with the host copies, every stream and the 16
+    readable bytes behind it inside `wire`, and both key indices inside the table."""
+    if nto < count or nscan < count or nresults < count:
+        raise ValueError("to / scan / results hold fewer than one record per stream")
+    if ndesc < desc_cap or nto_frames < desc_cap or nstatus < desc_cap or nnonces < desc_cap:
+        raise ValueError("desc / to_frames / status / nonces hold fewer than desc_cap records")
+    if out_bytes < wire_bytes:
+        raise ValueError("out is shorter than wire: it takes the same offsets")
+    if streams_np is not None and count:
+        s = streams_np[:count]
+        if len(s) < count or np.any(s["off"] + s["len"] + np.uint64(16) > np.uint64(wire_bytes)):
+            raise ValueError("stream out of bounds (wire must be readable for 16 bytes past its last stream)")
+        if nkeys is not None and np.any(s["key_idx"] >= nkeys):
+            raise ValueError("inbound key index out of bounds")
+    if to_np is not None and count:
+        if len(to_np) < count or (nkeys is not None and np.any(to_np["key_idx"][:count] >= nkeys)):
+            raise ValueError("outbound key index out of bounds")
+
+
+def relay_streams(streams, to, wire, out, scan, desc, to_frames, subkeys_t, status, nonces, results, maxmsgsize=-1,
+                  stream=None, desc_cap=None, streams_np=None, to_np=None):
+    """Re-seal many received V2 streams wire to wire (cz_relay_streams): `streams` a device tensor of
+    wire.V2_STREAM_DTYPE records, `to` one FANOUT_SUB_DTYPE record per stream (the outbound counter of its first
+    frame and the outbound subkey), `wire` the received bytes (readable for 16 bytes past the last stream), `out`
+    the same tensor (in place) or one of at least its size that takes the same offsets.  `scan` / `results` hold
+    one V2_STREAM_RESULT_DTYPE / RELAY_STREAM_RESULT_DTYPE record per stream; `desc` / `to_frames` / `status` /
+    `nonces` one record per frame.  Scan, one synchronisation for the totals, emit, relay, cut.  Of every
+    stream, send results[s].ok_bytes (or whole_bytes) and nothing behind them.  Returns (rc, nframes): rc is
+    CZ_OK, or CZ_ENOMEM with nframes filled and nothing written when it exceeds desc_cap (default: what `desc`
+    holds).  Any other failure raises.  With the host copies streams_np / to_np, bounds and key indices are
+    checked before the launch."""
+    from .wire import V2_STREAM_DTYPE, V2_STREAM_RESULT_DTYPE
+    _need_cuda_u8(wire, "wire")
+    _need_cuda_u8(out, "out")
+    _need_cuda_u8(subkeys_t, "subkeys")
+    for name, t in (("streams", streams), ("to", to), ("scan", scan), ("desc", desc), ("to_frames", to_frames),
+                    ("status", status), ("nonces", nonces), ("results", results)):
+        if t is None or not t.is_cuda:
+            raise ValueError(f"{name} must be a CUDA (HIP) tensor")
+    count = _nbytes(streams) // V2_STREAM_DTYPE.itemsize
+    if desc_cap is None:
+        desc_cap = _nbytes(desc) // DESC_DTYPE.itemsize
+    _check_relay_streams_bounds(count, _nbytes(to) // FANOUT_SUB_DTYPE.itemsize,
+                                _nbytes(scan) // V2_STREAM_RESULT_DTYPE.itemsize,
+                                _nbytes(results) // RELAY_STREAM_RESULT_DTYPE.itemsize, desc_cap,
+                                _nbytes(desc) // DESC_DTYPE.itemsize, _nbytes(to_frames) // FANOUT_SUB_DTYPE.itemsize,
+                                _nbytes(status) // 2, _nbytes(nonces) // 8, wire.numel(), out.numel(), streams_np, to_np,
+                                subkeys_t.shape[0])
+    tot = _lib.cz_v2_totals()
+    rc = _lib.lib().cz_relay_streams(_ptr(streams), _ptr(to), count, _ptr(wire), _ptr(out), maxmsgsize, _ptr(scan),
+                                     _ptr(desc), _ptr(to_frames), desc_cap, _ptr(subkeys_t), _ptr(status), _ptr(nonces),
+                                     _ptr(results), ctypes.byref(tot), _stream(stream))
+    if rc != _lib.CZ_ENOMEM:
+        _lib.check(rc, "cz_relay_streams")
+    return rc, int(tot.nframes)
+
+
 def fill(buf, seed, stream=None):
     """Counter-based SplitMix64 synthetic bytes (tests/cz_testlib.py splitmix_words)."""
     _lib.check(_lib.lib().cz_fill(_ptr(buf), buf.numel() * buf.element_size(), seed, _stream(stream)), "cz_fill")

@@ -26,7 +26,7 @@ LIB = os.environ.get("CZ_LIB_OUT", PRODUCT_LIB)
 # "file#n": the file compiled with -DCZ_KPART=n (cz_kernels.hip builds as three parts in parallel)
 SOURCES = ["cz_kernels.hip#1", "cz_kernels.hip#2", "cz_kernels.hip#3", "cz_x25519.hip", "cz_host.cpp", "cz_mechanism.cpp", "cz_wire.cpp", "cz_engine.cpp", "cz_handshake.cpp", "cz_curve_hs.cpp", "cz_hs_parse.cpp", "cz_acceptor.cpp", "cz_connector.cpp"]
 HEADERS = ["cz_accept.h", "cz_accept_kernels.h", "cz_connect.h", "cz_connect_kernels.h", "cz_hs_batch.h", "cz_hs_dev.h",
-           "cz_hs_records.h", "cz_hs_parse.h", "cz_device.h", "cz_fe25519.h", "cz_diag.h", "cz_dispatch.h", "cz_internal.h", "cz_launch.h", "cz_relay_kernels.h", "cz_salsa_lazy.h", "cz_salsa_tail.h", "cz_session.h", os.path.join("..", "..", "include", "curvezmq_mi355x.h")]
+           "cz_hs_records.h", "cz_hs_parse.h", "cz_device.h", "cz_fe25519.h", "cz_diag.h", "cz_dispatch.h", "cz_internal.h", "cz_launch.h", "cz_relay_kernels.h", "cz_routes.h", "cz_salsa_lazy.h", "cz_salsa_tail.h", "cz_session.h", os.path.join("..", "..", "include", "curvezmq_mi355x.h")]
 ARCH = os.environ.get("CZ_OFFLOAD_ARCH", "gfx950")
 LLVM_BIN = "/opt/rocm/lib/llvm/bin"
 BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"

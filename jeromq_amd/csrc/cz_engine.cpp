@@ -19,6 +19,10 @@
 //              bodies into aligned slots -> segmented open with the nonce floor chained frame to
 //              frame inside each connection (desc.prev) -> D2H -> per-connection delivery up to the
 //              first failing frame, whose status becomes the connection's error event.
+//   flush_forward: Proxy.forward (zmq/Proxy.java:140-160) for connections routed 1:1 with cz_engine_forward:
+//              the received bytes go over as they lie, are scanned and re-sealed in place for the destination
+//              (cz_relay_streams' chain, header section 3j), and come back as the destination's wire stream,
+//              cut at the first rejected frame.  No delivery, no plaintext in memory.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -29,6 +33,7 @@
 #include <vector>
 
 #include "cz_internal.h"
+#include "cz_routes.h"
 #include "cz_session.h"
 
 // pipeline depth of a large flush: groups of >= 8 MiB of wire bytes, at most this many.  At 1 GiB
@@ -152,6 +157,35 @@ struct RxPool {
     }
 };
 
+// Received bytes go to the device as they lie in the pinned receive blocks, one DMA per span: a run of
+// connections in address order, merged while they share a receive block and the bytes between them (other
+// connections' spare capacity) are at most MERGE_GAP -- copying those costs less than another DMA's gap.
+struct Span {
+    const uint8_t *src;
+    uint64_t dev, len;
+};
+
+// Where the next connection's `rx_len` received bytes go in d_wire: into the last span of spans[first ...] when
+// it merges, else a new span at `off`, the running device offset.  blk: the receive block of that last span.
+uint64_t place_in_spans(std::vector<Span> &spans, size_t first, uint32_t &blk, uint64_t &off, const RxBuf &rx,
+                        uint64_t rx_len)
+{
+    constexpr uint64_t MERGE_GAP = 1ull << 20;
+    Span *last = spans.size() > first ? &spans.back() : nullptr;
+    if (last && rx.blk == blk && rx.ptr <= last->src + last->len + MERGE_GAP) {
+        const uint64_t at = last->dev + (uint64_t)(rx.ptr - last->src);
+        const uint64_t end = (uint64_t)(rx.ptr + rx_len - last->src);
+        off += end - last->len;
+        last->len = end;
+        return at;
+    }
+    const uint64_t at = off;
+    spans.push_back({rx.ptr, off, rx_len});
+    off += rx_len;
+    blk = rx.blk;
+    return at;
+}
+
 struct Conn {
     bool server = false;
     uint32_t tx_key = 0, rx_key = 0;  // subkey table indices
@@ -164,6 +198,7 @@ struct Conn {
     std::vector<Run> runs;            // wire stream of the last flush_out: pieces of h_wire, in send order
     std::vector<uint8_t> gathered;    // contiguous copy for cz_engine_wire_out when runs > 1
     std::vector<uint32_t> in_msgs;    // indices into Engine::in_msgs of the last flush_in
+    uint64_t fwd_off = 0, fwd_len = 0;  // what the last flush_forward made of its received bytes: a piece of h_fwd
     bool removed = false;             // cz_engine_remove_conn: the id and its key slots await reuse
 };
 
@@ -263,6 +298,11 @@ struct cz_engine {
     // scanned flush: one cz_v2_stream per receiving connection, its cz_v2_stream_result, then the totals record
     DevBuf d_scan;
     HostBuf h_scan;
+    // forward routes (cz_engine_forward): flush_forward re-seals a routed connection's received stream in place
+    // for its destination; the wire bytes come back into h_fwd
+    RouteTable routes;
+    HostBuf h_fwd;
+    uint64_t forward_frames = 0;  // frames the last flush_forward forwarded
     HostBuf h_status, h_nonces;
     HostBuf h_meta;  // pinned staging of descriptors / items / segment lists (async H2D)
     RxPool rxpool;   // every connection's receive buffer
@@ -298,7 +338,7 @@ struct cz_engine {
                           &d_nonces, &d_plain, &d_subs, &d_fruns, &d_fwaves, &d_ftiles, &d_fjoins,
                           &d_fwork, &d_stage, &d_scan})
             b->release();
-        for (HostBuf *b : {&arena, &h_wire, &h_plain, &h_status, &h_nonces, &h_meta, &h_stage, &h_scan})
+        for (HostBuf *b : {&arena, &h_wire, &h_plain, &h_status, &h_nonces, &h_meta, &h_stage, &h_scan, &h_fwd})
             b->release();
     }
 
@@ -642,7 +682,7 @@ struct cz_engine {
         uint64_t rx_total = 0;
         for (size_t ci = 0; ci < conns.size(); ci++) {
             Conn &c = conns[ci];
-            if (c.error || c.rx_len == 0)
+            if (c.error || c.rx_len == 0 || routes.dest((int)ci) != -1)  // (a routed one waits for flush_forward)
                 continue;
             parsed.push_back({(uint32_t)ci, 0u, 0u, 0u, 0u, 0});
             rx_total += c.rx_len;
@@ -694,17 +734,10 @@ struct cz_engine {
         for (size_t gi = 0; gi < groups.size(); gi++)
             if ((e = hipEventCreateWithFlags(&ev[gi], hipEventDisableTiming)) != hipSuccess)
                 return hip_fail(e, "hipEventCreate");
-        // spans: a group's connections in address order, merged while they share a receive block
-        // and the bytes between them (other connections' spare capacity) are at most MERGE_GAP --
-        // copying those costs less than another DMA's gap
-        struct Span {
-            const uint8_t *src;
-            uint64_t dev, len;
-        };
+        // spans (place_in_spans): each group's connections in address order
         std::vector<Span> spans;
         std::vector<size_t> span_end(groups.size());
         {
-            constexpr uint64_t MERGE_GAP = 1ull << 20;
             uint64_t off = 0;
             std::vector<size_t> order;
             for (size_t gi = 0; gi < groups.size(); gi++) {
@@ -715,20 +748,8 @@ struct cz_engine {
                           [&](size_t x, size_t y) { return conns[parsed[x].conn].rx.ptr < conns[parsed[y].conn].rx.ptr; });
                 uint32_t blk = 0;
                 for (size_t pi : order) {
-                    Parsed &p = parsed[pi];
-                    const Conn &c = conns[p.conn];
-                    Span *last = spans.size() > (gi ? span_end[gi - 1] : 0) ? &spans.back() : nullptr;
-                    if (last && c.rx.blk == blk && c.rx.ptr <= last->src + last->len + MERGE_GAP) {
-                        p.rx_off = last->dev + (uint64_t)(c.rx.ptr - last->src);
-                        const uint64_t end = (uint64_t)(c.rx.ptr + c.rx_len - last->src);
-                        off += end - last->len;
-                        last->len = end;
-                    } else {
-                        p.rx_off = off;
-                        spans.push_back({c.rx.ptr, off, c.rx_len});
-                        off += c.rx_len;
-                        blk = c.rx.blk;
-                    }
+                    const Conn &c = conns[parsed[pi].conn];
+                    parsed[pi].rx_off = place_in_spans(spans, gi ? span_end[gi - 1] : 0, blk, off, c.rx, c.rx_len);
                 }
                 span_end[gi] = spans.size();
             }
@@ -1208,6 +1229,157 @@ struct cz_engine {
         pt.mark("deliver");
         return CZ_OK;
     }
+
+    // Forward routes (header section 3j): Proxy.forward for every routed connection at once, without delivery.
+    // On one stream, as the scanned flush: the sources' received bytes go over as they lie (one DMA per run of
+    // neighbours in the receive blocks), one cz_v2_stream and one cz_fanout_sub per route follow, the device
+    // scans and places the streams, the totals come back (the one extra synchronisation, which sizes the
+    // per-frame buffers), and then cz_relay_streams' chain runs IN PLACE: emit with materialised floors, one
+    // relay lane per frame, the cut.  The receive regions lie a region's spare capacity apart, so k_v2_copy
+    // (one item per route) packs the streams densely before they come back.  What comes back is the wire bytes,
+    // now the destinations' outbound streams, and 32 bytes per route; no per-frame record crosses PCIe in
+    // either direction.
+    int flush_forward()
+    {
+        PhaseTimer pt("flush_forward");
+        forward_frames = 0;
+        for (Conn &c : conns)
+            c.fwd_off = c.fwd_len = 0;
+        struct Route {
+            uint32_t from, to;
+            uint64_t off;    // where the source's received bytes start in d_wire
+            uint64_t dense;  // ... and in the packed copy that comes back into h_fwd
+        };
+        std::vector<Route> rt;
+        for (size_t ci = 0; ci < conns.size(); ci++) {
+            const int t = routes.dest((int)ci);
+            const Conn &c = conns[ci];
+            // (a failed destination: the source's bytes stay where they are)
+            if (t < 0 || c.error || c.rx_len == 0 || conns[(size_t)t].error)
+                continue;
+            if (c.rx_len > 0xffffffffull)
+                return fail(CZ_EINVAL, "cz_engine: more than 4 GiB received on routed connection %zu in one flush", ci);
+            rt.push_back({(uint32_t)ci, (uint32_t)t, 0, 0});
+        }
+        const uint32_t ns = (uint32_t)rt.size();
+        if (ns == 0)
+            return CZ_OK;
+        uint64_t dense = 0;
+        for (Route &r : rt) {
+            r.dense = dense;
+            dense += conns[r.from].rx_len;
+        }
+        // spans, as flush_in (place_in_spans): the sources in address order
+        std::vector<Span> spans;
+        uint64_t total = 0;
+        {
+            std::vector<uint32_t> order(ns);
+            for (uint32_t q = 0; q < ns; q++)
+                order[q] = q;
+            std::sort(order.begin(), order.end(),
+                      [&](uint32_t x, uint32_t y) { return conns[rt[x].from].rx.ptr < conns[rt[y].from].rx.ptr; });
+            uint32_t blk = 0;
+            for (uint32_t q : order) {
+                const Conn &c = conns[rt[q].from];
+                rt[q].off = place_in_spans(spans, 0, blk, total, c.rx, c.rx_len);
+            }
+        }
+        // one staging block: streams | outbound records | packing items | scan results | totals | cut results
+        const uint64_t o_to = (uint64_t)ns * sizeof(cz_v2_stream), o_items = o_to + (uint64_t)ns * sizeof(cz_fanout_sub),
+                       o_res = o_items + (uint64_t)ns * sizeof(cz_v2_item),
+                       o_tot = o_res + (uint64_t)ns * sizeof(cz_v2_stream_result), o_cut = o_tot + sizeof(cz_v2_totals),
+                       o_end = o_cut + (uint64_t)ns * sizeof(cz_relay_stream_result);
+        hipError_t e;
+        // (+ 16: a frame's replay floor is read at bytes [8, 16) of the frame before it where they lie)
+        if ((e = d_wire.reserve(total + 16)) != hipSuccess || (e = d_body.reserve(dense)) != hipSuccess ||
+            (e = h_fwd.reserve(dense)) != hipSuccess ||
+            (e = h_scan.reserve(o_end)) != hipSuccess || (e = d_scan.reserve(o_end)) != hipSuccess)
+            return hip_fail(e, "cz_engine: alloc");
+        uint8_t *hs = (uint8_t *)h_scan.ptr, *ds = (uint8_t *)d_scan.ptr;
+        cz_v2_stream *h_streams = (cz_v2_stream *)hs;
+        cz_fanout_sub *h_to = (cz_fanout_sub *)(hs + o_to);
+        cz_v2_item *h_items = (cz_v2_item *)(hs + o_items);
+        for (uint32_t q = 0; q < ns; q++) {
+            const Conn &f = conns[rt[q].from], &t = conns[rt[q].to];
+            h_streams[q] = {rt[q].off, f.rx_len, f.peer_nonce, f.rx_key, 0u};
+            h_to[q] = {t.nonce, t.tx_key, 0u};
+            h_items[q] = {rt[q].off, rt[q].dense, (uint32_t)f.rx_len, 0u};
+        }
+        const cz_v2_stream *d_streams = (const cz_v2_stream *)ds;
+        const cz_fanout_sub *d_to = (const cz_fanout_sub *)(ds + o_to);
+        cz_v2_stream_result *d_res = (cz_v2_stream_result *)(ds + o_res);
+        cz_relay_stream_result *d_cut = (cz_relay_stream_result *)(ds + o_cut);
+        const cz_v2_stream_result *h_res = (const cz_v2_stream_result *)(hs + o_res);
+        const cz_v2_totals *h_tot = (const cz_v2_totals *)(hs + o_tot);
+        const cz_relay_stream_result *h_cut = (const cz_relay_stream_result *)(hs + o_cut);
+        const hipStream_t qk = ps[1];
+        for (const Span &sp : spans)
+            if ((e = hipMemcpyAsync((uint8_t *)d_wire.ptr + sp.dev, sp.src, sp.len, hipMemcpyHostToDevice, qk)) !=
+                hipSuccess)
+                return hip_fail(e, "cz_engine: H2D");
+        if ((e = hipMemcpyAsync(ds, hs, o_res, hipMemcpyHostToDevice, qk)) != hipSuccess ||
+            (e = czk_v2_scan(d_streams, ns, d_wire.ptr, -1, 1u, d_res, (cz_v2_totals *)(ds + o_tot), qk)) != hipSuccess ||
+            (e = hipMemcpyAsync(hs + o_res, ds + o_res, o_cut - o_res, hipMemcpyDeviceToHost, qk)) != hipSuccess ||
+            (e = hipStreamSynchronize(qk)) != hipSuccess)
+            return hip_fail(e, "cz_engine: flush_forward scan");
+        pt.mark("h2d+scan");
+        if (h_tot->nframes > 0x7fffffffull)
+            return fail(CZ_EINVAL, "cz_engine: more than 2^31 - 1 received frames in one flush");
+        const uint32_t sn = (uint32_t)h_tot->nframes;
+        if (sn) {
+            if ((e = d_desc.reserve((uint64_t)sn * sizeof(cz_frame_desc))) != hipSuccess ||
+                (e = d_subs.reserve((uint64_t)sn * sizeof(cz_fanout_sub))) != hipSuccess ||
+                (e = d_status.reserve((uint64_t)sn * 2)) != hipSuccess ||
+                (e = d_nonces.reserve((uint64_t)sn * 8)) != hipSuccess)
+                return hip_fail(e, "cz_engine: alloc");
+            if ((e = czk_v2_emit_relay(d_streams, d_to, d_res, ns, d_wire.ptr, d_wire.ptr, (cz_frame_desc *)d_desc.ptr,
+                                       (cz_fanout_sub *)d_subs.ptr, qk)) != hipSuccess ||
+                (e = czk_relay_desc((const cz_frame_desc *)d_desc.ptr, (const cz_fanout_sub *)d_subs.ptr, nullptr, sn,
+                                    d_wire.ptr, d_wire.ptr, subkeys.ptr, (uint16_t *)d_status.ptr,
+                                    (uint64_t *)d_nonces.ptr, qk)) != hipSuccess)
+                return hip_fail(e, "cz_engine: flush_forward");
+        }
+        // (no frame at all: every lane of the cut writes the empty result without reading a per-frame record)
+        if ((e = czk_relay_cut(d_streams, d_res, ns, (const cz_frame_desc *)d_desc.ptr, (const uint16_t *)d_status.ptr,
+                               (const uint64_t *)d_nonces.ptr, d_cut, qk)) != hipSuccess ||
+            (e = hipMemcpyAsync(hs + o_cut, d_cut, o_end - o_cut, hipMemcpyDeviceToHost, qk)) != hipSuccess)
+            return hip_fail(e, "cz_engine: flush_forward");
+        if (sn && ((e = czk_v2_copy((const cz_v2_item *)(ds + o_items), ns, d_wire.ptr, d_body.ptr, qk)) != hipSuccess ||
+                   (e = hipMemcpyAsync(h_fwd.ptr, d_body.ptr, dense, hipMemcpyDeviceToHost, qk)) != hipSuccess))
+            return hip_fail(e, "cz_engine: D2H");
+        if ((e = hipStreamSynchronize(qk)) != hipSuccess)
+            return hip_fail(e, "cz_engine: flush_forward");
+        pt.mark("relay+d2h");
+        // what leaves, and the two ends' state: the source as flush_in leaves a receiver, the destination as
+        // flush_out leaves a sender of as many frames as were scanned (a rejected frame consumed its counter)
+        for (uint32_t q = 0; q < ns; q++) {
+            Conn &f = conns[rt[q].from], &t = conns[rt[q].to];
+            const cz_v2_stream_result &sr = h_res[q];
+            const cz_relay_stream_result &cr = h_cut[q];
+            f.fwd_off = rt[q].dense;
+            f.fwd_len = cr.ok_bytes;
+            f.peer_nonce = cr.peer_nonce;
+            t.nonce += sr.nframes;
+            forward_frames += cr.ok_frames;
+            if (cr.fail_status != CZ_STATUS_OK) {
+                f.error = CZ_EPROTO;
+                f.event = event_for(cr.fail_status, f.server);
+                f.rx_len = 0;
+                continue;
+            }
+            if (sr.consumed) {  // keep the partial frame for the next read
+                memmove(f.rx.ptr, (uint8_t *)f.rx.ptr + sr.consumed, f.rx_len - sr.consumed);
+                f.rx_len -= sr.consumed;
+            }
+            if (sr.rc) {  // V2Decoder error after the good frames: StreamEngine error(PROTOCOL)
+                f.error = sr.rc;
+                f.event = 0;
+                f.rx_len = 0;
+            }
+        }
+        pt.mark("deliver");
+        return CZ_OK;
+    }
 };
 
 namespace czi {
@@ -1412,6 +1584,7 @@ int cz_engine_remove_conn(cz_engine *e, int conn)
     dead.rx_key = c->rx_key;
     dead.removed = true;
     *c = std::move(dead);
+    e->routes.drop(conn);
     e->free_ids.push_back(conn);
     return CZ_OK;
 }
@@ -1489,6 +1662,7 @@ int cz_engine_remove_conns(cz_engine *e, uint32_t count, const int *conns, int32
         dead.rx_key = c.rx_key;
         dead.removed = true;
         c = std::move(dead);
+        e->routes.drop(id);
         e->free_ids.push_back(id);
     }
     return CZ_OK;
@@ -1706,6 +1880,43 @@ int cz_engine_flush_in(cz_engine *e)
     return rc;
 }
 
+int cz_engine_forward(cz_engine *e, int from, int to)
+{
+    if (!e)
+        return fail(CZ_EINVAL, "cz_engine_forward: null engine");
+    const auto live = [e](int id) { return id >= 0 && (size_t)id < e->conns.size() && !e->conns[(size_t)id].removed; };
+    if (!e->routes.set(from, to, live))
+        return fail(CZ_EINVAL,
+                    "cz_engine_forward: %d -> %d: an unknown connection, from == to, or a destination that has a source",
+                    from, to);
+    return CZ_OK;
+}
+
+int cz_engine_flush_forward(cz_engine *e)
+{
+    if (!e)
+        return fail(CZ_EINVAL, "cz_engine_flush_forward: null engine");
+    hipError_t he = hipSetDevice(e->device);
+    if (he != hipSuccess)
+        return hip_fail(he, "hipSetDevice");
+    const int rc = e->flush_forward();
+    if (rc != CZ_OK)
+        e->drain();  // an error return may leave copies into/out of the pinned buffers in flight
+    return rc;
+}
+
+int cz_engine_forward_out(cz_engine *e, int from, const uint8_t **wire, uint64_t *len)
+{
+    if (!e || !wire || !len)
+        return fail(CZ_EINVAL, "cz_engine_forward_out: null pointer");
+    Conn *c = e->conn(from);
+    if (!c)
+        return CZ_EINVAL;
+    *wire = (const uint8_t *)e->h_fwd.ptr + c->fwd_off;
+    *len = c->fwd_len;
+    return CZ_OK;
+}
+
 int cz_engine_msgs_in(cz_engine *e, int conn, uint32_t *count)
 {
     if (!e || !count)
@@ -1760,5 +1971,6 @@ uint64_t cz_engine_peer_nonce(cz_engine *e, int conn)
 uint64_t cz_engine_fanin_frames(const cz_engine *e) { return e ? e->fanin_frames : 0; }
 uint64_t cz_engine_scan_frames(const cz_engine *e) { return e ? e->scan_frames : 0; }
 uint64_t cz_engine_fanin_split_frames(const cz_engine *e) { return e ? e->fanin_split_frames : 0; }
+uint64_t cz_engine_forward_frames(const cz_engine *e) { return e ? e->forward_frames : 0; }
 
 }  // extern "C"

@@ -4060,6 +4060,101 @@ __global__ __launch_bounds__(BLOCK) void k_v2_emit(const cz_v2_stream *__restric
     }
 }
 
+// Emit for the stream relay (cz_relay_streams, header section 3j): the same walk, writing for frame k of
+// stream s at index first + k the relay's descriptor -- the body re-sealed where it lies (out_off == in_off)
+// -- and its outbound record {to[s].counter + k, to[s].key_idx}.  The replay floor of frame k > 0 is
+// MATERIALISED here: the big-endian u64 at bytes [8, 16) of frame k - 1's body as it lies on the wire (what
+// k_relay_desc reads through prev, also when that body is shorter than 16 bytes), read before the relay
+// launch can store over it.  So no descriptor has a prev, and the in-place relay is legal.  out != wire:
+// the frame's 2 or 9 header bytes are copied over as well, byte-exact; nothing else of `out` is written.
+// (`wire` and `out` may be the same bytes: neither is __restrict__.)
+__global__ __launch_bounds__(BLOCK) void k_v2_emit_relay(const cz_v2_stream *__restrict__ streams,
+                                                          const cz_fanout_sub *__restrict__ to,
+                                                          const cz_v2_stream_result *__restrict__ results,
+                                                          uint32_t count, const uint8_t *wire, uint8_t *out,
+                                                          cz_frame_desc *__restrict__ desc,
+                                                          cz_fanout_sub *__restrict__ to_frames)
+{
+    const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
+    if (s >= count)
+        return;
+    const cz_v2_stream st = streams[s];
+    const cz_fanout_sub dst = to[s];
+    const cz_v2_stream_result res = results[s];
+    const V2Stream v = v2_stream(wire, st);
+    u64 p = 0, floor = st.floor;
+    for (u32 k = 0; k < res.nframes && p < v.len; k++) {
+        u32 flags, h;
+        u64 size;
+        if (v2_step(v, p, -1, flags, h, size))
+            break;
+        const u64 i = (u64)res.first + k;
+        const u64 body = st.off + p + h;
+        cz_frame_desc d;
+        d.in_off = body;
+        d.out_off = body;
+        d.len = (u32)size;
+        d.key_idx = st.key_idx;
+        d.counter = floor;
+        d.flags = CZ_DESC_CHECK_NONCE;
+        d.prev = -1;
+        desc[i] = d;
+        cz_fanout_sub t;
+        t.counter = dst.counter + k;
+        t.key_idx = dst.key_idx;
+        t.reserved = 0;
+        to_frames[i] = t;
+        if (out != wire)
+            for (u32 b = 0; b < h; b++)
+                out[st.off + p + b] = wire[st.off + p + b];
+        if (k + 1u < res.nframes)  // (inside the stream, or within 16 bytes behind it when this body is short)
+            floor = read_be64(wire + body + 8);
+        p += h + size;
+    }
+}
+
+// Cut for the stream relay, behind k_relay_desc: lane s walks the statuses of its stream's frames up to the
+// first rejected one.  ok_bytes: the wire bytes of the frames before it; whole_bytes: cut back to the end of
+// the last of those whose decrypted flags byte lacks MORE; peer_nonce by the engine's delivery rule (the
+// last accepted frame's wire nonce; a CRYPTO frame's nonce passed the replay check before its tag failed;
+// else the stream's floor).
+__global__ __launch_bounds__(BLOCK) void k_relay_cut(const cz_v2_stream *__restrict__ streams,
+                                                      const cz_v2_stream_result *__restrict__ results, uint32_t count,
+                                                      const cz_frame_desc *__restrict__ desc,
+                                                      const uint16_t *__restrict__ status,
+                                                      const uint64_t *__restrict__ nonces,
+                                                      cz_relay_stream_result *__restrict__ cut)
+{
+    const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
+    if (s >= count)
+        return;
+    const cz_v2_stream st = streams[s];
+    const cz_v2_stream_result res = results[s];
+    cz_relay_stream_result r;
+    r.ok_bytes = 0;
+    r.whole_bytes = 0;
+    r.peer_nonce = st.floor;
+    r.ok_frames = 0;
+    r.fail_status = CZ_STATUS_OK;
+    r.reserved = 0;
+    for (u32 k = 0; k < res.nframes; k++) {
+        const u64 i = (u64)res.first + k;
+        const u32 w = status[i];
+        if ((w & 0xffu) != CZ_STATUS_OK) {
+            r.fail_status = (uint16_t)(w & 0xffu);
+            if (r.fail_status == CZ_STATUS_CRYPTO)
+                r.peer_nonce = nonces[i];
+            break;
+        }
+        r.ok_bytes = desc[i].in_off + desc[i].len - st.off;
+        if (!((w >> 8) & 1u))
+            r.whole_bytes = r.ok_bytes;
+        r.peer_nonce = nonces[i];
+        r.ok_frames = k + 1u;
+    }
+    cut[s] = r;
+}
+
 // ---- one NaCl box per launch (the jnacl crypto_box_afternm / open_afternm drop-ins) ----------
 // One call used to be a chain of copies and launches (subkey, segments, combine, wipe): ~50 us at
 // 4 KiB against ~11 us for a bare launch + sync (tools/diag/latency_ub.hip).  This kernel does the
@@ -4824,6 +4919,30 @@ hipError_t czk_v2_emit(const cz_v2_stream *streams, const cz_v2_stream_result *r
         return hipSuccess;
     hipLaunchKernelGGL(k_v2_emit, dim3((count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, streams, results, count,
                        (const uint8_t *)wire, slot_align, frames, desc);
+    return hipGetLastError();
+}
+
+// stream relay (header section 3j): the relay's descriptors and outbound records, one lane per stream ...
+hipError_t czk_v2_emit_relay(const cz_v2_stream *streams, const cz_fanout_sub *to, const cz_v2_stream_result *results,
+                             uint32_t count, const void *wire, void *out, cz_frame_desc *desc, cz_fanout_sub *to_frames,
+                             hipStream_t s)
+{
+    if (count == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(k_v2_emit_relay, dim3((count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, streams, to, results,
+                       count, (const uint8_t *)wire, (uint8_t *)out, desc, to_frames);
+    return hipGetLastError();
+}
+
+// ... and, behind the relay, what of each stream may leave
+hipError_t czk_relay_cut(const cz_v2_stream *streams, const cz_v2_stream_result *results, uint32_t count,
+                         const cz_frame_desc *desc, const uint16_t *status, const uint64_t *nonces,
+                         cz_relay_stream_result *cut, hipStream_t s)
+{
+    if (count == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(k_relay_cut, dim3((count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, streams, results, count, desc,
+                       status, nonces, cut);
     return hipGetLastError();
 }
 

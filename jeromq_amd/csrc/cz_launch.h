@@ -64,6 +64,15 @@ hipError_t czk_v2_scan(const cz_v2_stream *streams, uint32_t count, const void *
                        uint32_t slot_align, cz_v2_stream_result *results, cz_v2_totals *totals, hipStream_t s);
 hipError_t czk_v2_emit(const cz_v2_stream *streams, const cz_v2_stream_result *results, uint32_t count,
                        const void *wire, uint32_t slot_align, cz_v2_frame *frames, cz_frame_desc *desc, hipStream_t s);
+// stream relay: the walk once more writes the relay's descriptors (materialised floors, no prev, bodies where
+// they lie) and per-frame outbound records, and the headers when out != wire (k_v2_emit_relay); behind
+// czk_relay_desc, one lane per stream cuts its stream at the first rejected frame (k_relay_cut)
+hipError_t czk_v2_emit_relay(const cz_v2_stream *streams, const cz_fanout_sub *to, const cz_v2_stream_result *results,
+                             uint32_t count, const void *wire, void *out, cz_frame_desc *desc, cz_fanout_sub *to_frames,
+                             hipStream_t s);
+hipError_t czk_relay_cut(const cz_v2_stream *streams, const cz_v2_stream_result *results, uint32_t count,
+                         const cz_frame_desc *desc, const uint16_t *status, const uint64_t *nonces,
+                         cz_relay_stream_result *cut, hipStream_t s);
 
 // CURVE relay: received bodies re-sealed for another peer in one pass (descriptor batch; one connection to one)
 hipError_t czk_relay_desc(const cz_frame_desc *desc, const cz_fanout_sub *to, const uint32_t *order, uint32_t count,

@@ -6,7 +6,8 @@
 // header per frame (the bodies are never touched here) and runs on the host, while the byte movement
 // (packing sealed bodies behind their headers, unpacking received bodies into aligned slots)
 // runs on the device in k_v2_copy.  MANY streams are as many independent walks: cz_v2_scan /
-// cz_v2_scan_emit / cz_open_streams run them on the device, one lane per stream, with the same rules.
+// cz_v2_scan_emit / cz_open_streams / cz_relay_streams run them on the device, one lane per stream, with the
+// same rules.
 #include <stdint.h>
 #include <string.h>
 
@@ -107,6 +108,24 @@ static thread_local struct {
     int device = -1;
 } t_totals;
 
+// that record for the current device
+static hipError_t thread_totals(cz_v2_totals **d_totals)
+{
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess)
+        return e;
+    if (dev != t_totals.device) {
+        t_totals.buf = DevBuf{};
+        t_totals.device = -1;
+        if ((e = t_totals.buf.reserve(sizeof(cz_v2_totals))) != hipSuccess)
+            return e;
+        t_totals.device = dev;
+    }
+    *d_totals = (cz_v2_totals *)t_totals.buf.ptr;
+    return hipSuccess;
+}
+
 int cz_open_streams(const cz_v2_stream *d_streams, uint32_t count, const void *d_wire, int64_t maxmsgsize,
                     uint32_t slot_align, cz_v2_stream_result *d_results, cz_frame_desc *d_desc, uint64_t desc_cap,
                     void *d_out, uint64_t out_cap, const void *d_subkeys, uint16_t *d_status, uint64_t *d_nonces,
@@ -121,18 +140,10 @@ int cz_open_streams(const cz_v2_stream *d_streams, uint32_t count, const void *d
     if (count == 0)
         return CZ_OK;
     hipStream_t s = (hipStream_t)stream;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    cz_v2_totals *d_totals = nullptr;
+    hipError_t e = thread_totals(&d_totals);
     if (e != hipSuccess)
         return hip_fail(e, "cz_open_streams");
-    if (dev != t_totals.device) {
-        t_totals.buf = DevBuf{};
-        t_totals.device = -1;
-        if ((e = t_totals.buf.reserve(sizeof(cz_v2_totals))) != hipSuccess)
-            return hip_fail(e, "cz_open_streams: hipMalloc");
-        t_totals.device = dev;
-    }
-    cz_v2_totals *d_totals = (cz_v2_totals *)t_totals.buf.ptr;
     if ((e = czk_v2_scan(d_streams, count, d_wire, maxmsgsize, slot_align, d_results, d_totals, s)) != hipSuccess ||
         (e = hipMemcpyAsync(h_totals, d_totals, sizeof *h_totals, hipMemcpyDeviceToHost, s)) != hipSuccess ||
         (e = hipStreamSynchronize(s)) != hipSuccess)
@@ -147,6 +158,44 @@ int cz_open_streams(const cz_v2_stream *d_streams, uint32_t count, const void *d
         (e = czk_open_desc(d_desc, nullptr, (uint32_t)h_totals->nframes, d_wire, d_out, d_subkeys, d_status, d_nonces,
                            s)) != hipSuccess)
         return hip_fail(e, "cz_open_streams: open");
+    return CZ_OK;
+}
+
+// Section 3j: cz_open_streams' chain with the relay in the open's place.  The emit materialises every frame's
+// replay floor before the relay stores anything, so the bodies are re-sealed where they lie; the cut then says
+// what of each stream may leave.
+int cz_relay_streams(const cz_v2_stream *d_streams, const cz_fanout_sub *d_to, uint32_t count, const void *d_wire,
+                     void *d_out, int64_t maxmsgsize, cz_v2_stream_result *d_scan, cz_frame_desc *d_desc,
+                     cz_fanout_sub *d_to_frames, uint64_t desc_cap, const void *d_subkeys, uint16_t *d_status,
+                     uint64_t *d_nonces, cz_relay_stream_result *d_results, cz_v2_totals *h_totals, void *stream)
+{
+    if (!h_totals)
+        return fail(CZ_EINVAL, "cz_relay_streams: null pointer");
+    *h_totals = {0, 0};
+    if (count == 0)
+        return CZ_OK;
+    if (!d_streams || !d_to || !d_wire || !d_out || !d_scan || !d_desc || !d_to_frames || !d_subkeys || !d_status ||
+        !d_nonces || !d_results)
+        return fail(CZ_EINVAL, "cz_relay_streams: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    cz_v2_totals *d_totals = nullptr;
+    hipError_t e = thread_totals(&d_totals);
+    if (e != hipSuccess)
+        return hip_fail(e, "cz_relay_streams");
+    if ((e = czk_v2_scan(d_streams, count, d_wire, maxmsgsize, 1u, d_scan, d_totals, s)) != hipSuccess ||
+        (e = hipMemcpyAsync(h_totals, d_totals, sizeof *h_totals, hipMemcpyDeviceToHost, s)) != hipSuccess ||
+        (e = hipStreamSynchronize(s)) != hipSuccess)
+        return hip_fail(e, "cz_relay_streams: scan");
+    if (h_totals->nframes > 0x7fffffffull)
+        return fail(CZ_EINVAL, "cz_relay_streams: %llu frames, more than 2^31 - 1", (unsigned long long)h_totals->nframes);
+    if (h_totals->nframes > desc_cap)
+        return fail(CZ_ENOMEM, "cz_relay_streams: %llu frames exceed desc_cap %llu",
+                    (unsigned long long)h_totals->nframes, (unsigned long long)desc_cap);
+    if ((e = czk_v2_emit_relay(d_streams, d_to, d_scan, count, d_wire, d_out, d_desc, d_to_frames, s)) != hipSuccess ||
+        (e = czk_relay_desc(d_desc, d_to_frames, nullptr, (uint32_t)h_totals->nframes, d_wire, d_out, d_subkeys,
+                            d_status, d_nonces, s)) != hipSuccess ||
+        (e = czk_relay_cut(d_streams, d_scan, count, d_desc, d_status, d_nonces, d_results, s)) != hipSuccess)
+        return hip_fail(e, "cz_relay_streams: relay");
     return CZ_OK;
 }
 

@@ -11,6 +11,8 @@ device batch per flush and socket-ready ZMTP v2 wire streams per connection.
     eng.recv(c, received_bytes); eng.flush_in()
     for payload, flags in eng.messages_in(c): ...
     eng.error(c)                                              # (CZ_EPROTO, ZMTP event) after a failure
+    eng.forward(a, b); eng.recv(a, received_bytes)            # a broker's route: what a receives leaves for b,
+    eng.flush_forward(); wire = eng.forward_out(a)            # re-sealed in place, without delivery
 """
 import ctypes
 
@@ -226,6 +228,32 @@ class CurveBatchEngine:
         opened from the wire bytes where they lie.  The whole flush or nothing: cz_tune("scan_in") = n > 0,
         at least 64 connections with received bytes, none holding more than n."""
         return int(self._L.cz_engine_scan_frames(self._h))
+
+    # ---- forward routes: a broker's Proxy.forward without the plaintext reaching memory ----
+
+    def forward(self, from_, to):
+        """Route everything `from_` receives to `to`, re-sealed (cz_engine_forward); to=-1 or None clears the
+        route.  One source per destination; A -> B with B -> A is the normal proxy.  flush_in skips a routed
+        connection: its bytes wait for flush_forward."""
+        _lib.check(self._L.cz_engine_forward(self._h, from_, -1 if to is None else to), "cz_engine_forward")
+
+    def flush_forward(self):
+        """Re-seal every routed connection's received whole frames in place for its destination, in one device
+        chain; what leaves is cut at the first rejected frame, which fails the source as flush_in would."""
+        _lib.check(self._L.cz_engine_flush_forward(self._h), "cz_engine_flush_forward")
+
+    def forward_out(self, conn):
+        """The bytes the last flush_forward made of `conn`'s received stream: wire frames for the socket of its
+        route's destination."""
+        p, n = ctypes.c_void_p(), ctypes.c_uint64()
+        _lib.check(self._L.cz_engine_forward_out(self._h, conn, ctypes.byref(p), ctypes.byref(n)),
+                   "cz_engine_forward_out")
+        return ctypes.string_at(p.value, n.value) if n.value else b""
+
+    @property
+    def forward_frames(self):
+        """Frames the last flush_forward forwarded."""
+        return int(self._L.cz_engine_forward_frames(self._h))
 
     def messages_in(self, conn):
         cnt = ctypes.c_uint32()

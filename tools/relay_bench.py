@@ -24,6 +24,13 @@ at seg_blocks = batch.SEG_BLOCKS:
 over 1024 bodies of 65569 bytes under 1024 key pairs; 2^16 frames of the Zipf 64 B .. 64 KiB length mix of
 bench.py's zipf config; 2^16 bodies of 1 KiB payload (nothing is split).  16-byte aligned slots.
 
+--streams measures the stream relay (cz_relay_streams, header section 3j) and the engine's forward routes instead
+and writes profiles/relay/relay_streams.json.  Device leg, 1024 streams x 16 frames of 100 B, 1 KiB and 4 KiB
+payloads and 64 streams x 1 frame of 4 KiB, four sides alternating: cz_relay_streams in place and out of place,
+cz_open_streams + cz_seal_batch + cz_v2_copy(CZ_V2_ITEM_HEADER), and the host parse + cz_relay_batch.  Engine leg,
+1024 routes x 16 frames: cz_engine_flush_forward against flush_in + send of every message + flush_out on a second
+broker fed the same bytes.
+
 Writes profiles/relay/relay.json and prints it.  --log2 / --batch-log2 / --host-log2 shrink the shapes for a
 rehearsal; the committed file is measured at the defaults.  --pmc: one call of each side at the first uniform
 shape, for a counter run:
@@ -294,6 +301,235 @@ def segments_main(args, torch, dev, batch, build, _lib):
                      {"legs": [{k: v for k, v in r.items() if not k.endswith("_all_ms")} for r in out["legs"]]}))
 
 
+STREAM_KERNELS = ["k_v2_scan", "k_v2_place", "k_v2_emit_relay", "k_relay_desc", "k_relay_cut"]
+# (name, streams, frames per stream, payload bytes)
+STREAM_SHAPES = (("1024x16_100b", 1024, 16, 100), ("1024x16_1k", 1024, 16, 1024), ("1024x16_4k", 1024, 16, 4096),
+                 ("64x1_4k", 64, 1, 4096))
+
+
+def prepared(torch, legs, reps):
+    """alternate() for legs that need their input restored first: legs = {name: (prepare, fn)}; only fn is timed
+    (a host clock between two synchronisations: every side synchronises inside or is short)"""
+    def once(prep, fn):
+        prep()
+        return wall_ms(torch, fn)
+    for prep, fn in legs.values():
+        once(prep, fn)
+    times = {k: [] for k in legs}
+    for _ in range(reps):
+        for k, (prep, fn) in legs.items():
+            times[k].append(once(prep, fn))
+    row = {}
+    for k, t in times.items():
+        med = statistics.median(t)
+        row[k + "_ms"] = round(med, 5)
+        row[k + "_min_ms"], row[k + "_max_ms"] = round(min(t), 5), round(max(t), 5)
+        row[k + "_spread"] = round((max(t) - min(t)) / med, 4)
+        row[k + "_all_ms"] = [round(v, 5) for v in t]
+    return row
+
+
+def streams_device_leg(args, torch, dev, batch, wire, name, nstreams, nframes, length):
+    """`nstreams` received streams of `nframes` frames, each under its own key pair, packed back to back.
+    in_place / out_of_place: cz_relay_streams.  open_seal_pack: cz_open_streams, cz_seal_batch, cz_v2_copy with
+    CZ_V2_ITEM_HEADER, the seal's descriptors and the copy's items built once outside the clock.  host_parse:
+    cz_v2_parse per stream on the host, descriptors with prev chains built and uploaded, cz_relay_batch."""
+    size = length + 33
+    hdr = 9 if size > 255 else 2
+    count = nstreams * nframes
+    keys = torch.empty(2 * nstreams * 32, dtype=torch.uint8, device=dev)
+    batch.fill(keys, 7)
+    keys = keys.view(2 * nstreams, 32)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)  # noqa: E731
+    idx = np.arange(count, dtype=np.uint64)
+    s_of, k_of = idx // np.uint64(nframes), idx % np.uint64(nframes)
+    pslot, bslot, fb = round_up(max(length, 1), 128), round_up(size, 16), hdr + size
+    # the received wire: payloads sealed under the inbound keys, packed behind their V2 headers
+    plain = torch.empty(count * pslot + 64, dtype=torch.uint8, device=dev)
+    batch.fill(plain, 13)
+    sd = np.zeros(count, dtype=batch.DESC_DTYPE)
+    sd["in_off"], sd["out_off"], sd["len"], sd["key_idx"] = idx * pslot, idx * bslot, length, 2 * s_of
+    sd["counter"], sd["prev"] = 100 + k_of, -1
+    bodies = torch.zeros(count * bslot + 64, dtype=torch.uint8, device=dev)
+    batch.seal_batch(up(sd), count, plain, bodies, keys, desc_np=sd)
+    items = np.zeros(count, dtype=wire.V2_ITEM_DTYPE)
+    items["src_off"], items["dst_off"], items["size"], items["flags"] = idx * bslot, idx * fb, size, 0x100
+    d_items = up(items)
+    total = count * fb
+    orig = torch.zeros(total + 64, dtype=torch.uint8, device=dev)
+    wire.copy(d_items, bodies, orig)
+    st = np.zeros(nstreams, dtype=wire.V2_STREAM_DTYPE)
+    st["off"], st["len"] = np.arange(nstreams, dtype=np.uint64) * (nframes * fb), nframes * fb
+    st["floor"], st["key_idx"] = 99, 2 * np.arange(nstreams)
+    to = np.zeros(nstreams, dtype=batch.FANOUT_SUB_DTYPE)
+    to["counter"], to["key_idx"] = 1 << 40, 2 * ((np.arange(nstreams) * 7 + 1) % nstreams) + 1
+    d_st, d_to = wire.to_device(st, dev), wire.to_device(to, dev)
+    z = lambda n: torch.zeros(n, dtype=torch.uint8, device=dev)  # noqa: E731
+    work, outs = orig.clone(), {k: z(total + 64) for k in ("out_of_place", "open_seal_pack", "host_parse")}
+    scan, cut, desc, tof = z(nstreams * 32), z(nstreams * 32), z(count * 40), z(count * 16)
+    status = {k: torch.full((count,), -1, dtype=torch.int16, device=dev)
+              for k in ("in_place", "out_of_place", "open_seal_pack", "host_parse")}
+    nonces = torch.zeros(count, dtype=torch.int64, device=dev)
+    # side B's second and third call: seal from the open's plaintext slots into body slots, pack behind headers
+    td = sd.copy()
+    td["key_idx"], td["counter"] = to["key_idx"][s_of.astype(np.int64)], (1 << 40) + k_of
+    d_td, body2 = up(td), z(count * bslot + 64)
+    h_wire = orig.cpu().numpy()
+    nothing = lambda: None  # noqa: E731
+
+    def in_place():
+        batch.relay_streams(d_st, d_to, work, work, scan, desc, tof, keys, status["in_place"], nonces, cut)
+
+    def out_of_place():
+        batch.relay_streams(d_st, d_to, orig, outs["out_of_place"], scan, desc, tof, keys, status["out_of_place"], nonces,
+                            cut)
+
+    def open_seal_pack():
+        batch.open_streams(d_st, orig, scan, desc, plain, keys, status["open_seal_pack"], nonces=nonces, slot_align=128)
+        batch.seal_batch(d_td, count, plain, body2, keys)
+        wire.copy(d_items, body2, outs["open_seal_pack"])
+
+    def host_parse():
+        rd = np.zeros(count, dtype=batch.DESC_DTYPE)
+        at = 0
+        for s in range(nstreams):
+            o, n = int(st["off"][s]), int(st["len"][s])
+            frames, _consumed, _rc = wire.parse(h_wire[o:o + n], cap=nframes + 1)
+            r = rd[at:at + len(frames)]
+            r["in_off"] = r["out_off"] = frames["body_off"] + np.uint64(o)
+            r["len"], r["key_idx"], r["counter"], r["flags"] = frames["size"], st["key_idx"][s], 99, 0x100
+            r["prev"] = np.arange(at - 1, at - 1 + len(frames))
+            r["prev"][0] = -1
+            at += len(frames)
+        tf = np.zeros(count, dtype=batch.FANOUT_SUB_DTYPE)
+        tf["counter"], tf["key_idx"] = td["counter"], td["key_idx"]
+        batch.relay_batch(up(rd), up(tf), count, orig, outs["host_parse"], keys, status["host_parse"])
+
+    legs = {"in_place": (lambda: work.copy_(orig), in_place), "out_of_place": (nothing, out_of_place),
+            "open_seal_pack": (nothing, open_seal_pack), "host_parse": (nothing, host_parse)}
+    for prep, fn in legs.values():
+        prep()
+        fn()
+    torch.cuda.synchronize()
+    assert all(int((s != 0).sum()) == 0 for s in status.values()), "a body was rejected"
+    assert torch.equal(work[:total], outs["out_of_place"][:total]), "in place and out of place disagree"
+    assert torch.equal(work[:total], outs["open_seal_pack"][:total]), "cz_relay_streams and open + seal + pack disagree"
+    b = outs["host_parse"].view(-1)[:total].view(count, fb)[:, hdr:]
+    assert torch.equal(work[:total].view(count, fb)[:, hdr:], b), "cz_relay_streams and parse + cz_relay_batch disagree"
+    row = {"leg": name, "streams": nstreams, "frames_per_stream": nframes, "payload": length, "wire_bytes": total}
+    row.update(prepared(torch, legs, args.reps))
+    for k in ("in_place", "out_of_place"):
+        row[k + "_over_open_seal_pack"] = round(row[k + "_ms"] / row["open_seal_pack_ms"], 4)
+        row[k + "_over_host_parse"] = round(row[k + "_ms"] / row["host_parse_ms"], 4)
+    return row
+
+
+def streams_engine_leg(args, torch, _lib, name, nroutes, nframes, length):
+    """flush_forward of `nroutes` routes x `nframes` frames against flush_in + cz_engine_send of every delivered
+    message + flush_out on a second broker; a peer engine makes fresh traffic for every repetition, and both
+    brokers have received it before the clock starts.  two_flushes: the second broker's two flush calls alone."""
+    import ctypes
+
+    from jeromq_amd.engine import CurveBatchEngine
+    L = _lib.lib()
+    arena = max(1 << 22, 2 * nroutes * nframes * (length + 64))
+    peer, br, br2 = (CurveBatchEngine(arena_bytes=arena) for _ in range(3))
+    pre = bytes(range(32))
+    p = peer.add_connections([pre] * nroutes, as_server=False)
+    ends = []
+    for e in (br, br2):
+        src = e.add_connections([pre] * nroutes, as_server=True)
+        dst = e.add_connections([pre] * nroutes, as_server=True)
+        ends.append((src, dst))
+    for s, d in zip(*ends[0]):
+        br.forward(s, d)
+    payload = bytes(length)
+    t = {"forward": [], "flush_in_send_flush_out": [], "two_flushes": []}
+    pp, n, fl = ctypes.c_void_p(), ctypes.c_uint32(), ctypes.c_int()
+    cnt = ctypes.c_uint32()
+    for rep in range(args.reps + 1):
+        for c in p:
+            for _ in range(nframes):
+                peer.send(c, payload)
+        peer.flush_out()
+        for k, c in enumerate(p):
+            w = peer.wire_out(c)
+            br.recv(ends[0][0][k], w)
+            br2.recv(ends[1][0][k], w)
+        f_ms = wall_ms(torch, br.flush_forward)
+        t0 = time.perf_counter()
+        br2.flush_in()
+        t1 = time.perf_counter()
+        for s, d in zip(*ends[1]):
+            L.cz_engine_msgs_in(br2._h, s, ctypes.byref(cnt))
+            for i in range(cnt.value):
+                L.cz_engine_msg_in(br2._h, s, i, ctypes.byref(pp), ctypes.byref(n), ctypes.byref(fl))
+                L.cz_engine_send(br2._h, d, pp, n, fl)
+        t2 = time.perf_counter()
+        br2.flush_out()
+        t3 = time.perf_counter()
+        assert br.forward_frames == nroutes * nframes
+        same = all(br.forward_out(s) == br2.wire_out(d) for s, d in list(zip(ends[0][0], ends[1][1]))[:8])
+        assert same, "flush_forward and flush_in + send + flush_out disagree"
+        if rep:     # (the first round warms both)
+            t["forward"].append(f_ms)
+            t["flush_in_send_flush_out"].append((t3 - t0) * 1e3)
+            t["two_flushes"].append((t1 - t0 + t3 - t2) * 1e3)
+    for e in (peer, br, br2):
+        e.close()
+    row = {"leg": name, "routes": nroutes, "frames_per_route": nframes, "payload": length}
+    for k, v in t.items():
+        med = statistics.median(v)
+        row[k + "_ms"], row[k + "_spread"] = round(med, 4), round((max(v) - min(v)) / med, 4)
+        row[k + "_all_ms"] = [round(x, 4) for x in v]
+    row["forward_over_flush_in_send_flush_out"] = round(row["forward_ms"] / row["flush_in_send_flush_out_ms"], 4)
+    row["forward_over_two_flushes"] = round(row["forward_ms"] / row["two_flushes_ms"], 4)
+    return row
+
+
+def streams_main(args, torch, dev, batch, build, _lib):
+    from jeromq_amd import wire
+    out = {"device": torch.cuda.get_device_name(0), "library": _lib.lib().cz_version().decode(),
+           "stream_kernels_sha256": build.kernel_code_sha256(_lib.LIB_PATH, STREAM_KERNELS), "reps": args.reps,
+           "sides": {"in_place": "cz_relay_streams, d_out = d_wire (the wire restored outside the clock)",
+                     "out_of_place": "cz_relay_streams into a second buffer",
+                     "open_seal_pack": "cz_open_streams, cz_seal_batch, cz_v2_copy with CZ_V2_ITEM_HEADER; the seal's "
+                                       "descriptors and the copy's items are built outside the clock",
+                     "host_parse": "cz_v2_parse per stream (driven from Python), descriptors with prev chains built and "
+                                   "uploaded, cz_relay_batch",
+                     "forward": "cz_engine_flush_forward",
+                     "flush_in_send_flush_out": "cz_engine_flush_in, cz_engine_msg_in + cz_engine_send of every message "
+                                                "through ctypes, cz_engine_flush_out on a second broker",
+                     "two_flushes": "that broker's flush_in and flush_out alone, the send loop left out"},
+           "clock": "time.perf_counter between two synchronisations around one call of a side, median of the alternations",
+           "spread": "(max - min) / median of a side's alternations", "legs": [], "engine_legs": []}
+    path = args.out if args.out else os.path.join(ROOT, "profiles", "relay", "relay_streams.json")
+
+    def write():
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+    shrink = args.streams_shrink
+    for name, ns, nf, length in STREAM_SHAPES:
+        out["legs"].append(streams_device_leg(args, torch, dev, batch, wire, name, max(ns // shrink, 1), nf, length))
+        torch.cuda.empty_cache()
+        write()
+    for name, ns, nf, length in STREAM_SHAPES[:3]:
+        out["engine_legs"].append(streams_engine_leg(args, torch, _lib, name, max(ns // shrink, 1), nf, length))
+        write()
+    for r in out["legs"]:
+        print(f"{r['leg']}: in place {r['in_place_ms']} ms, out of place {r['out_of_place_ms']} ms, open + seal + pack "
+              f"{r['open_seal_pack_ms']} ms, host parse + relay {r['host_parse_ms']} ms", file=sys.stderr)
+    for r in out["engine_legs"]:
+        print(f"engine {r['leg']}: forward {r['forward_ms']} ms, flush_in + send + flush_out "
+              f"{r['flush_in_send_flush_out_ms']} ms, the two flushes alone {r['two_flushes_ms']} ms", file=sys.stderr)
+    strip = lambda rows: [{k: v for k, v in r.items() if not k.endswith("_all_ms")} for r in rows]  # noqa: E731
+    print(json.dumps({k: v for k, v in out.items() if k not in ("legs", "engine_legs")} |
+                     {"legs": strip(out["legs"]), "engine_legs": strip(out["engine_legs"])}))
+
+
 def host_leg(args, torch, dev, batch):
     count, size, ist, pst = 1 << args.host_log2, 4129, 4224, 4096
     keys = torch.empty(64, dtype=torch.uint8, device=dev)
@@ -349,7 +585,12 @@ def main():
                     help="measure cz_relay_segments against cz_relay_batch and open_segments + seal_segments instead; "
                          "writes profiles/relay/relay_segments.json")
     ap.add_argument("--seg-log2", type=int, default=16, help="--segments: log2 of the frame count of the ragged legs")
-    ap.add_argument("--out", default=None, help="default: profiles/relay/relay.json (relay_segments.json with --segments)")
+    ap.add_argument("--streams", action="store_true",
+                    help="measure cz_relay_streams and cz_engine_flush_forward against the routes they replace instead; "
+                         "writes profiles/relay/relay_streams.json")
+    ap.add_argument("--streams-shrink", type=int, default=1, help="--streams: divide the stream counts (a rehearsal)")
+    ap.add_argument("--out", default=None, help="default: profiles/relay/relay.json (relay_segments.json with --segments, "
+                                                "relay_streams.json with --streams)")
     args = ap.parse_args()
     if args.reps < (12 if args.segments else 10):
         ap.error("--reps: at least 10 alternations (--segments: 12)")
@@ -361,6 +602,9 @@ def main():
     dev = torch.device("cuda:0")
     if args.segments:
         segments_main(args, torch, dev, batch, build, _lib)
+        return
+    if args.streams:
+        streams_main(args, torch, dev, batch, build, _lib)
         return
     args.out = args.out or os.path.join(ROOT, "profiles", "relay", "relay.json")
     if args.pmc:
